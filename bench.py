@@ -19,6 +19,13 @@ the reference apportions `reads*chrWL/WL`.  No data-path collective.
 including ingest: ranks own whole contigs balanced by length, ingest only those (simuReads --rank/--world).
 `--workload c4` is the same for the tumour mixture of BASELINE configs[4]: four populations with variants and SNPs, 60x
 (bench_c3.py).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line; the figures
+of those same steps (kernel times, roofline of the live launch) come with it.  Everything that takes work of its own is
+behind `--full`: the pinned-host legs, the md5 of the last pass, the CPU baseline, the strong-scaling leg and the committed
+counter passes quoted in `roofline` (the `--no-*` and `--strong-scale` options trim a `--full` run).
+`--dump-outputs DIR` writes what the last timed step computed (its sizes, a fixed sample of both mates' FASTQ text and the
+byte sums of every 64 KiB of it) as .npy files; the inputs are the same from run to run, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -198,6 +205,55 @@ def host_pinned_rate(sess, steps, gzip):
             "pcie_GBps": moved[0] / dt / 1e9, "bytes_per_step": moved[0] / steps}
 
 
+DUMP_SAMPLE_CHUNKS = 64        # chunks of each mate's text in the dump: the first, the last and 62 at seeded places
+DUMP_SAMPLE_BYTES = 1 << 16    # bytes per chunk (float32 in the file: 2 mates x 64 x 64 KiB x 4 B = 32 MiB)
+DUMP_SUM_BLOCK = 1 << 16       # the whole text's byte sums are taken per block of this many bytes
+
+
+def dump_outputs(sess, out_dir):
+    """What the last timed step handed its caller, as .npy files in `out_dir`: `counts` (mate-1 bytes, mate-2 bytes,
+    pairs), and per mate a fixed sample of the FASTQ text (`mateM_text_sample`, bytes as float32, chunks at offsets drawn
+    once from a fixed seed as fractions of the text) and the byte sum of every DUMP_SUM_BLOCK bytes of the whole text
+    (`mateM_block_sums`, float64).  The text is copied off the device through one pinned buffer."""
+    import ctypes as C
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    b1, b2, nf = sess.result()
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([b1, b2, nf], dtype=np.float64))
+    fracs = np.random.default_rng(20241015).random(DUMP_SAMPLE_CHUNKS - 2)
+    CH = 1 << 26
+    host = sess.host_alloc(CH)
+    try:
+        view = np.frombuffer((C.c_char * CH).from_address(host), dtype=np.uint8)
+
+        def fetch(mate, off, n):
+            sess._sg(sess.eng.sg_fetch_range(sess.ctx, mate, off, n, C.c_void_p(host)), "sg_fetch_range")
+            return view[:n]
+
+        for mate, total in ((0, b1), (1, b2)):
+            if not total:
+                continue
+            span = max(total - DUMP_SAMPLE_BYTES, 0)
+            offs = [0, span] + [int(f * span) for f in fracs]
+            sample = np.zeros((DUMP_SAMPLE_CHUNKS, DUMP_SAMPLE_BYTES), dtype=np.float32)
+            for i, off in enumerate(offs):
+                n = min(DUMP_SAMPLE_BYTES, total - off)
+                sample[i, :n] = fetch(mate, off, n)
+            np.save(os.path.join(out_dir, f"mate{mate + 1}_text_sample.npy"), sample)
+            sums = np.zeros((total + DUMP_SUM_BLOCK - 1) // DUMP_SUM_BLOCK, dtype=np.float64)
+            for off in range(0, total, CH):   # CH is a multiple of DUMP_SUM_BLOCK: blocks never straddle two copies
+                n = min(CH, total - off)
+                part = fetch(mate, off, n)
+                full = n // DUMP_SUM_BLOCK * DUMP_SUM_BLOCK
+                k = off // DUMP_SUM_BLOCK
+                sums[k:k + full // DUMP_SUM_BLOCK] = part[:full].reshape(-1, DUMP_SUM_BLOCK).sum(axis=1, dtype=np.uint64)
+                if full < n:
+                    sums[-1] = float(part[full:n].sum(dtype=np.uint64))
+            np.save(os.path.join(out_dir, f"mate{mate + 1}_block_sums.npy"), sums)
+    finally:
+        sess.host_free(host)
+
+
 def relaunch_under_torchrun(args):
     """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) as a child torchrun and relay its
     output.  Nothing here has touched the GPU yet (no torch import, no engine): the child processes do."""
@@ -224,9 +280,14 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="c3: contig lengths = GRCh38 primary lengths x scale")
     ap.add_argument("--contig-len", type=int, default=CHR20_LEN)
     ap.add_argument("--coverage", type=int, default=None, help="default: 30 (c2, c3), 60 (c4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-pinned", action="store_true", help="skip the pinned-host legs (plain + gzip) after the timed region")
-    ap.add_argument("--no-md5", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: pinned-host legs, md5 of the last pass, CPU baseline, strong-scaling "
+                         "leg, committed counter passes in `roofline` (each of them can be left out with the options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (c2 workload, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-host-pinned", action="store_true", help="--full: skip the pinned-host legs (plain + gzip) after the timed region")
+    ap.add_argument("--no-md5", action="store_true", help="--full: skip the md5 of the last pass")
     ap.add_argument("--profile", default="xten", choices=sorted(PROFILES),
                     help="sequencing profile of the workload (default: HiSeqXTen, the configuration the metric is quoted on)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
@@ -234,9 +295,15 @@ def main():
                     help="make a process group even for ONE rank (also SIMUSCOP_FORCE_PG=1): the all_gather of the read balancing, "
                          "the max/sum all-reduces and the strong leg's exchange then run through RCCL on the one GPU at hand")
     ap.add_argument("--strong-scale", type=float, default=None,
-                    help="c2: size of the genome of the strong-scaling leg (24 contigs, GRCh38 lengths x this; default 1.0, 0.25 on hosts "
-                         "with fewer than 16 cores; 0 = no leg)")
+                    help="c2 --full: size of the genome of the strong-scaling leg (24 contigs, GRCh38 lengths x this; default 1.0, 0.25 on "
+                         "hosts with fewer than 16 cores; 0 = no leg)")
     args = ap.parse_args()
+    if not args.full:
+        if args.strong_scale:
+            raise SystemExit("bench.py: the strong-scaling leg (--strong-scale) is part of --full")
+        args.no_cpu_baseline = args.no_host_pinned = args.no_md5 = True
+    if args.dump_outputs and args.workload != "c2":
+        raise SystemExit("bench.py: --dump-outputs is for the c2 workload (c3 / c4 steps keep no output)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args)
@@ -249,6 +316,8 @@ def main():
     if args.coverage is None:
         args.coverage = 30
     strong_scale = args.strong_scale if args.strong_scale is not None else (1.0 if (os.cpu_count() or 1) >= 16 else 0.25)
+    if not args.full:
+        strong_scale = 0
     if strong_scale:   # the leg's genome: made (by rank 0, on all host cores) before anything here touches the GPU
         import bench_c3
         bench_c3.ensure_genome(strong_scale, int(os.environ.get("RANK", "0")))
@@ -339,6 +408,8 @@ def main():
         dt_max, total_pairs = float(tmax[0]), float(tsum[1])
     else:
         dt_max, total_pairs = dt, float(pairs)
+    if rank == 0 and args.dump_outputs:   # before anything below samples another pass
+        dump_outputs(sess, args.dump_outputs)
 
     if rank == 0:
         default_workload = args.contig_len == CHR20_LEN and args.coverage == 30 and args.profile == "xten"
@@ -350,7 +421,7 @@ def main():
         total_items = 2.0 * pairs_per_step * ((L + 7) // 8)
         main_share = 1.0 - queued_items / max(total_items, 1.0)
         achieved = pairs_per_step * bytes_per_pair * main_share / (emit_ms * 1e-3) / 1e9
-        pmc = pmc_evidence() if default_workload else None
+        pmc = pmc_evidence() if default_workload and args.full else None
         pmc_stale = None
         if pmc:
             # Counters of another build say nothing about this one: they are quoted only when they were taken on exactly the
@@ -388,7 +459,7 @@ def main():
             "config": {"workload": f"C2: one {args.contig_len} bp contig per GPU" + (" (GRCh38 chr20 length)" if args.contig_len == CHR20_LEN else "") + f", {PROFILES[args.profile][0][:-8]} profile "
                                    f"({L} bp), PE, {args.coverage}x, insertSize 350",
                        "pairs_per_step_per_gpu": pairs_per_step, "parallelism": f"{world} x 1 chromosome shard"},
-            "value_counts": "pairs whose FASTQ text is complete in HBM (inputs resident); the pinned-host rates are in host_pinned",
+            "value_counts": "pairs whose FASTQ text is complete in HBM (inputs resident); the pinned-host rates are in host_pinned (--full)",
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
                          "frac": achieved / 8000.0,
                          # PMC traffic was collected on the default workload only

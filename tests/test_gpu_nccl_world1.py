@@ -26,7 +26,7 @@ def _last_json(text):
 @pytest.mark.timeout(600)
 def test_bench_line_through_rccl_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-process-group", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-process-group", "--steps", "2", "--warmup", "1",
                         "--contig-len", "3000000", "--strong-scale", "0.01", "--no-cpu-baseline", "--no-host-pinned", "--no-md5"],
                        capture_output=True, text=True, timeout=580, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -279,7 +279,7 @@ def test_default_bench_line_on_two_ranks():
     import json
     import sys
     from simuscop_amd import synth
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
                         "--contig-len", "8000000", "--strong-scale", "0.02", "--no-md5"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, BENCH_SAME_DEVICE="1"))
     assert r.returncode == 0, r.stderr[-3000:]

@@ -7,20 +7,16 @@ sg_train_*) against this restatement, byte for byte."""
 import ctypes as C
 import hashlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cases
 import histo_util as H
+import ref_runs
 import simuscop_amd
 import test_train_counts as TC
 import train_util as TU
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref", "simuReads")
-SHIM = os.path.join(ROOT, "oracle", "_ref", "libfakeclock.so")
 
 
 def declare(lib):
@@ -78,7 +74,6 @@ def test_trained_profile_has_the_shape_of_a_shipped_one(trained):
     assert 0 < P["Insert Rate"][0][0] < 1 and 0 < P["Deletion Rate"][0][0] < 1
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference binary not built (make -C oracle ref; needs /root/reference)")
 @pytest.mark.parametrize("layout", ["PE", "SE"])
 def test_reference_binary_loads_the_trained_profile_and_samples_like_the_oracle(layout, trained, oracle_lib, tmp_path):
     """Profile::load of the unmodified binary reads the written file; a run from it is, byte for byte, oracle(mt)'s."""
@@ -86,16 +81,14 @@ def test_reference_binary_loads_the_trained_profile_and_samples_like_the_oracle(
     out = os.path.join(str(tmp_path), "out")
     cases._config(cfg, ref=trained["fa1"], profile=trained["profile"], name="t", output=out, layout=layout, threads=1, verbose=0,
                   coverage=2, insertSize=350, ploidy=2)
-    env = dict(os.environ, LD_PRELOAD=SHIM, FAKECLOCK_SEC=str(cases.FAKE_SEC), FAKECLOCK_NSEC=str(cases.FAKE_NSEC))
-    r = subprocess.run([REF, cfg], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-1000:]
-    md5 = lambda d: {f: hashlib.md5(open(os.path.join(d, f), "rb").read()).hexdigest() for f in sorted(os.listdir(d))}   # noqa: E731
-    want = md5(out)
-    assert want and all(os.path.getsize(os.path.join(out, f)) > 1_000_000 for f in want)
-    for f in os.listdir(out):
-        os.remove(os.path.join(out, f))
+    # (the record was written from this very profile file: its md5 is part of the key)
+    key = f"train/{layout}/" + hashlib.md5(open(trained["profile"], "rb").read()).hexdigest()
+    rc, want = ref_runs.run(key, cfg, out, timeout=600)
+    assert rc == 0
+    assert want and len(want) == (2 if layout == "PE" else 1)
     assert oracle_lib.orc_simulate(cfg.encode(), 0, cases.FAKE_SEC, cases.FAKE_NSEC, b"", 1) == 0, oracle_lib.orc_last_error().decode()
-    assert md5(out) == want
+    assert all(os.path.getsize(os.path.join(out, f)) > 1_000_000 for f in want)
+    assert ref_runs.md5s(out) == want
 
 
 def test_count_gc_turns_reads_away_and_opens_windows(trained, oracle_lib):

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 for v in "$@"; do
   env $v python3 - "$v" <<'PY'
 import json, os, subprocess, sys
-r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--strong-scale", "0", "--no-cpu-baseline", "--no-md5"], capture_output=True, text=True)
+r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--strong-scale", "0", "--no-cpu-baseline", "--no-md5"], capture_output=True, text=True)
 d = json.loads(r.stdout.strip().splitlines()[-1])
 hp = d["host_pinned"]
 print(sys.argv[1], "ratio %.3f" % (hp["plain"]["bytes_per_step"] / hp["gzip"]["bytes_per_step"]), "gzip %.1f M pairs/s" % (hp["gzip"]["value"] / 1e6),

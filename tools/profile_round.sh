@@ -30,6 +30,6 @@ from simuscop_amd.build import engine_source_digest
 d["_meta"] = {"emit_fast_kernel_avg_ms": ms, "from": "kernel_stats.csv of the same profile_round.sh run", "engine_source_digest": engine_source_digest()}
 json.dump(d, open(out + "/pmc_summary.json", "w"), indent=1)
 PY
-python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 rm -rf $out/trace gpurun_out/pmc_${tag}_*
 ls -la $out
