@@ -375,6 +375,34 @@ void sg_train_end(sg_ctx* ctx);
 int sg_train_count(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes, const char* const* contig_keys, uint32_t n_contigs,
                    const char* bases, int32_t kmer, int32_t bins, uint32_t n_isize, uint32_t n_indel_len, sg_train_counts* out);
 
+/* ---- BGZF and BAM input (SAMv1 sections 4.1-4.2): seqToProfile -b x.bam --decode-bam without samtools ----
+ * A BGZF file is a run of gzip members (RFC 1952), each with the extra subfield 'BC' holding BSIZE (member bytes - 1) and at
+ * most 64 KiB of input (ISIZE), closed by the 28-byte empty member of sg_bgzf_eof.  The members are inflated on the device
+ * (stored, fixed- and dynamic-Huffman blocks; CRC-32 and ISIZE checked); a member that is not well formed is SG_ERR_INVALID
+ * and the message names its file offset.
+ *   sg_bgzf_members  host only: the member headers of `bytes` bytes -- offset, BSIZE, ISIZE of up to `cap` whole members
+ *                    (any of the arrays may be NULL); *whole_bytes = the bytes they make up (a member cut by the end of the
+ *                    buffer is not one of them).  SG_ERR_INVALID for a header that is not BGZF (sg_last_error(NULL) says where)
+ *   sg_inflate_bgzf  whole members in host memory -> their inflated bytes in `out`; *out_bytes = how many there are
+ *                    (SG_ERR_OVERFLOW when out_cap is too small: call again).  For the BAM header, and tests
+ * In a training session (after sg_train_begin) the records of a BAM file take the place of the lines of text:
+ *   sg_train_bam_start  the header's reference names (refID order) and where in the decompressed stream the first record
+ *                    starts (behind magic, l_text, text, n_ref and the reference list); call once, before any feed
+ *   sg_train_feed_bgzf  whole members in file order, from the file's first byte.  Record boundaries are found on the
+ *                    device, records that straddle calls are carried over; every record `samtools view -F 0xD04 -q 20`
+ *                    prints becomes the line it prints (eleven fields, QNAME and RNEXT / PNEXT included, a CIGAR of more
+ *                    than 65,535 operations from its CG:B:I tag), and the lines go through the kernels of sg_train_feed.
+ *                    Same contract: the members are copied before the call returns, the verdict of the lines arrives with
+ *                    the next call, the cap ends the reading (sg_train_capped).  A malformed member or record is SG_ERR_INVALID
+ *                    at once.  `bytes` = 0 ends the stream: SG_ERR_INVALID when a record was left unfinished
+ *   sg_train_bam_info   records decoded (kept or not), bytes inflated, seconds spent in sg_train_feed_bgzf so far      */
+int sg_bgzf_members(const void* buf, uint64_t bytes, uint64_t* offsets, uint32_t* bsize, uint32_t* isize, uint64_t cap, uint64_t* n_members,
+                    uint64_t* whole_bytes);
+int sg_inflate_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes, void* out, uint64_t out_cap, uint64_t* out_bytes);
+int sg_train_bam_start(sg_ctx* ctx, const char* const* ref_names, uint32_t n_ref, uint64_t first_record_skip);
+int sg_train_feed_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes);
+int sg_train_bam_info(sg_ctx* ctx, uint64_t* records, uint64_t* inflated_bytes, double* seconds);
+
 /* Which emit kernel the loaded profile gets (after sg_load_profile): 0 generic (tables that do not fit
  * LDS, k-mer sizes other than 3), 1 straight-line kernel (table image in LDS). */
 int sg_emit_variant(sg_ctx* ctx);

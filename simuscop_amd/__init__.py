@@ -29,6 +29,7 @@ ENGINE_SYMBOLS = [
     "sg_sub_row_identity_first", "sg_row_symbols", "sg_alias_row", "sg_window_weights", "sg_windows_build", "sg_plan_windows", "sg_plan_range", "sg_windows_drop",
     "sg_host_free", "sg_profile_prepare", "sg_profile_tables_error", "sg_load_prepared_profile", "sg_profile_tables_free", "sg_train_count",
     "sg_train_begin", "sg_train_feed", "sg_train_capped", "sg_train_finish", "sg_train_end",
+    "sg_bgzf_members", "sg_inflate_bgzf", "sg_train_bam_start", "sg_train_feed_bgzf", "sg_train_bam_info",
     "sg_release_cached_memory",
 ]
 
@@ -155,6 +156,12 @@ def load_engine():
     lib.sg_train_finish.argtypes = [vp, C.POINTER(SgTrainCounts), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.POINTER(C.c_uint64)]
     lib.sg_train_end.argtypes = [vp]
     lib.sg_train_end.restype = None
+    lib.sg_bgzf_members.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.sg_inflate_bgzf.argtypes = [vp, C.c_char_p, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.sg_train_bam_start.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64]
+    lib.sg_train_feed_bgzf.argtypes = [vp, C.c_char_p, C.c_uint64]
+    lib.sg_train_bam_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     lib.sg_build_haplotypes.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(SgHapPiece), C.c_uint64,
                                         C.c_char_p, C.c_uint64, C.POINTER(SgHapPatch), C.c_uint64]
     lib.sg_haplotype_codes.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p]
@@ -262,18 +269,20 @@ class SimuTrainOptions(C.Structure):
     """simu_train_options (host/train.h): the options of the reference's seqToProfile + the additive ones"""
     _fields_ = [("bam", C.c_char_p), ("sam", C.c_char_p), ("target", C.c_char_p), ("vcf", C.c_char_p), ("ref", C.c_char_p),
                 ("output", C.c_char_p), ("samtools", C.c_char_p), ("kmer", C.c_int32), ("bins", C.c_int32), ("device", C.c_int32),
-                ("threads", C.c_int32), ("quiet", C.c_int32), ("stamp", C.c_char_p), ("max_reads", C.c_uint64)]
+                ("threads", C.c_int32), ("quiet", C.c_int32), ("stamp", C.c_char_p), ("max_reads", C.c_uint64),
+                ("decode_bam", C.c_int32)]
 
 
 class SimuTrainStats(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("reads_counted", C.c_uint64), ("gc_rejected", C.c_uint64), ("gc_windows", C.c_uint64),
                 ("gc_pairs", C.c_uint64), ("skipped_overhang", C.c_uint64), ("sam_bytes", C.c_uint64), ("read_length", C.c_int32),
                 ("bins", C.c_int32), ("gc_fitted", C.c_int32), ("capped", C.c_int32), ("t_reference", C.c_double), ("t_reads", C.c_double), ("t_total", C.c_double),
-                ("insert_rate", C.c_double), ("del_rate", C.c_double), ("std_isize", C.c_double), ("gc_std", C.c_double)]
+                ("insert_rate", C.c_double), ("del_rate", C.c_double), ("std_isize", C.c_double), ("gc_std", C.c_double),
+                ("bam_bytes", C.c_uint64), ("bam_records", C.c_uint64), ("t_inflate", C.c_double)]
 
 
 def train_profile(ref: str, vcf: str, output: str, sam: str = "", bam: str = "", target: str = "", samtools: str = "", kmer: int = 3,
-                  bins: int = 50, device: int = 0, quiet: int = 1, stamp: str = None, max_reads: int = 0) -> SimuTrainStats:
+                  bins: int = 50, device: int = 0, quiet: int = 1, stamp: str = None, max_reads: int = 0, decode_bam: bool = False) -> SimuTrainStats:
     """`seqToProfile` in-process (src/seqToProfile.cpp main): reads (`sam`: a file of `samtools view` text, or `bam` through
     samtools as the reference does), the sample's VCF and the reference -> a .profile file; the per-read work runs on the GPU."""
     lib = load_host()
@@ -284,6 +293,7 @@ def train_profile(ref: str, vcf: str, output: str, sam: str = "", bam: str = "",
     lib.simu_train_default_options(C.byref(o))
     o.bam, o.sam, o.target, o.vcf, o.ref, o.output, o.samtools = (x.encode() for x in (bam, sam, target, vcf, ref, output, samtools))
     o.kmer, o.bins, o.device, o.quiet, o.max_reads = kmer, bins, device, quiet, max_reads
+    o.decode_bam = 1 if decode_bam else 0
     if stamp is not None:
         o.stamp = stamp.encode()
     st = SimuTrainStats()

@@ -253,6 +253,183 @@ struct ChunkReader {
   }
 };
 
+// ---- --decode-bam: the BAM file itself, read in batches of whole BGZF members (SAMv1 section 4.1) ----
+constexpr uint64_t kBamBatch = 16ull << 20;   // compressed bytes per batch (about 3 to 4 times as many inflated)
+constexpr uint32_t kMaxMember = 65536;        // BSIZE is 16 bits
+
+uint32_t le32(const uint8_t* p) { return p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// Pinned batches cut at a member boundary, read ahead while the device works on the batch before: a regular file by the pread
+// pool, standard input by fread.  A member cut by the end of the file is an error.
+struct BamReader {
+  sg_ctx* ctx;
+  std::string what;
+  FILE* fp = nullptr;
+  int fd = -1;
+  uint64_t pos = 0, size = 0, file_off = 0;   // file_off: where the next batch starts
+  std::unique_ptr<ReaderPool> pool;
+  char* buf[2] = {nullptr, nullptr};
+  uint64_t len[2] = {0, 0};
+  std::string pending;   // bytes behind the last whole member of a batch
+  std::string last28;    // the last 28 bytes read (the EOF member, if the file has one)
+  bool eof = false;
+  BamReader(sg_ctx* c, const std::string& path, int threads) : ctx(c), what(path) {
+    if (path == "-") fp = stdin;
+    else if (!(fp = fopen(path.c_str(), "rb"))) throw Error("cannot open BAM file " + path, -1);
+    struct stat sb;
+    if (fp != stdin && fstat(fileno(fp), &sb) == 0 && S_ISREG(sb.st_mode)) {
+      fd = fileno(fp);
+      size = (uint64_t)sb.st_size;
+      pool.reset(new ReaderPool(std::min(16, std::max(1, threads))));
+    }
+    for (int i = 0; i < 2; i++) {
+      void* p = nullptr;
+      if (sg_host_alloc(ctx, kBamBatch + kMaxMember, &p) != SG_OK) throw Error(std::string("GPU engine error in sg_host_alloc: ") + sg_last_error(ctx));
+      buf[i] = (char*)p;
+    }
+  }
+  ~BamReader() {
+    for (char* b : buf) if (b) sg_host_free(ctx, b);
+    if (fp && fp != stdin) fclose(fp);
+  }
+  void rewind() { pos = 0; file_off = 0; pending.clear(); last28.clear(); eof = false; }
+  bool eof_marker() const {
+    uint8_t e[28];
+    sg_bgzf_eof(e);
+    return last28.size() == 28 && memcmp(last28.data(), e, 28) == 0;
+  }
+  // fills buf[i] with whole members; false when nothing is left
+  bool fill(int i) {
+    if (eof && pending.empty()) { len[i] = 0; return false; }
+    uint64_t have = pending.size();
+    const uint64_t p0 = have;
+    memcpy(buf[i], pending.data(), have);
+    pending.clear();
+    if (fd >= 0) {
+      const uint64_t n = std::min<uint64_t>(kBamBatch + kMaxMember - have, size - pos);
+      if (n) parallel_pread(*pool, fd, (uint8_t*)buf[i] + have, pos, n);
+      have += n;
+      pos += n;
+      if (pos >= size) eof = true;
+    } else {
+      while (!eof && have < kBamBatch + kMaxMember) {
+        const size_t got = fread(buf[i] + have, 1, kBamBatch + kMaxMember - have, fp);
+        if (got == 0) { eof = true; break; }
+        have += got;
+      }
+    }
+    {
+      const uint64_t fresh = have - p0, k = std::min<uint64_t>(fresh, 28);
+      const std::string t = last28 + std::string(buf[i] + have - k, k);
+      last28 = t.substr(t.size() > 28 ? t.size() - 28 : 0);
+    }
+    uint64_t n_members = 0, whole = 0;
+    if (sg_bgzf_members(buf[i], have, nullptr, nullptr, nullptr, ~0ull, &n_members, &whole) != SG_OK)
+      throw Error("Error: corrupt BGZF member at file offset " + std::to_string(file_off + whole) + " of " + what);
+    pending.assign(buf[i] + whole, have - whole);
+    if (eof && !pending.empty())
+      throw Error("Error: truncated BGZF member at file offset " + std::to_string(file_off + whole) + " of " + what);
+    len[i] = whole;
+    file_off += whole;
+    return whole > 0;
+  }
+};
+
+// The header (magic, l_text, text, n_ref, the reference list) and the read length: the first record `samtools view
+// -F 0xD04 -q 20` prints whose CIGAR is a single nM, searched over the whole stream (Profile::setReadLength, Profile.cpp:155-163).
+// Inflated with the device inflater; the batches a pipe gave are kept for the training pass, a file is read again.
+struct BamHeader {
+  std::vector<std::string> names;
+  uint64_t bytes = 0;   // where the first record starts in the decompressed stream
+};
+int bam_record_single_match(const uint8_t* r, uint32_t bs) {
+  const int32_t ref = (int32_t)le32(r + 4), pos = (int32_t)le32(r + 8), lseq = (int32_t)le32(r + 20);
+  const uint32_t lname = r[12], mapq = r[13], ncig = r[16] | ((uint32_t)r[17] << 8), flag = r[18] | ((uint32_t)r[19] << 8);
+  if ((flag & 0xD04u) || mapq < 20 || lseq < 0) return 0;
+  const uint64_t cig = 36 + lname, aux = cig + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq, end = 4ull + bs;
+  if (aux > end) return 0;
+  const uint8_t* ops = r + cig;
+  uint32_t nops = ncig;
+  if (ncig > 0 && ref >= 0 && pos >= 0 && (ops[0] & 15u) == 4 && (le32(ops) >> 4) == (uint32_t)lseq) {   // htslib's bam_tag2cigar
+    uint64_t p = aux;
+    auto size_of = [](uint8_t t) -> uint32_t { return strchr("AcC", t) ? 1 : strchr("sS", t) ? 2 : strchr("iIf", t) ? 4 : t == 'd' ? 8 : 0; };
+    while (p + 3 <= end) {
+      const uint8_t t0 = r[p], t1 = r[p + 1], ty = r[p + 2];
+      p += 3;
+      if (ty == 'Z' || ty == 'H') { while (p < end && r[p]) p++; p++; continue; }
+      if (ty == 'B') {
+        if (p + 5 > end || !ty) break;
+        const uint8_t sub = r[p];
+        const uint32_t n = le32(r + p + 1), es = sub ? size_of(sub) : 0;
+        if (!es) break;
+        if (t0 == 'C' && t1 == 'G' && (sub == 'I' || sub == 'i')) {
+          if (n >= ncig && n < (1u << 29) && p + 5 + 4ull * n <= end) { ops = r + p + 5; nops = n; }
+          break;
+        }
+        p += 5 + (uint64_t)n * es;
+        continue;
+      }
+      const uint32_t es = ty ? size_of(ty) : 0;
+      if (!es) break;
+      p += es;
+    }
+  }
+  if (nops == 1 && (ops[0] & 15u) == 0) return (int)(le32(ops) >> 4);
+  return 0;
+}
+
+void bam_prepare(sg_ctx* ctx, BamReader& rd, BamHeader& H, int& read_length, std::vector<std::string>& replay) {
+  std::string dec;        // inflated bytes not yet looked at
+  uint64_t dec_off = 0;   // their offset in the stream
+  bool have_header = false, more = true;
+  std::vector<char> out(kBamBatch * 8);
+  while (more && !read_length) {
+    more = rd.fill(0);
+    if (!more) break;
+    if (rd.fd < 0) replay.emplace_back(rd.buf[0], rd.len[0]);
+    uint64_t n = 0;
+    int rc = sg_inflate_bgzf(ctx, rd.buf[0], rd.len[0], out.data(), out.size(), &n);
+    if (rc == SG_ERR_OVERFLOW) { out.resize(n); rc = sg_inflate_bgzf(ctx, rd.buf[0], rd.len[0], out.data(), out.size(), &n); }
+    if (rc != SG_OK) throw Error(std::string("GPU engine error in sg_inflate_bgzf: ") + sg_last_error(ctx) + " (" + rd.what + ")");
+    dec.append(out.data(), n);
+    size_t p = 0;
+    if (!have_header) {
+      const uint8_t* d = (const uint8_t*)dec.data();
+      if (dec.size() < 12) continue;
+      if (memcmp(d, "BAM\1", 4) != 0) throw Error("Error: " + rd.what + " is not a BAM file (bad magic)");
+      const uint64_t l_text = le32(d + 4);
+      if (l_text > (1ull << 31) || dec.size() < 12 + l_text) continue;
+      const uint32_t n_ref = le32(d + 8 + l_text);
+      uint64_t q = 12 + l_text;
+      std::vector<std::string> names;
+      bool whole = true;
+      for (uint32_t i = 0; i < n_ref; i++) {
+        if (q + 4 > dec.size()) { whole = false; break; }
+        const uint32_t l_name = le32(d + q);
+        if (l_name < 1 || l_name > (1u << 20)) throw Error("Error: malformed BAM header in " + rd.what);
+        if (q + 4 + l_name + 4 > dec.size()) { whole = false; break; }
+        names.emplace_back((const char*)d + q + 4, strnlen((const char*)d + q + 4, l_name));
+        q += 4 + l_name + 4;
+      }
+      if (!whole) continue;
+      H.names = names;
+      H.bytes = q;
+      have_header = true;
+      p = q;
+    }
+    while (!read_length && dec.size() - p >= 4) {
+      const uint32_t bs = le32((const uint8_t*)dec.data() + p);
+      if (bs < 32) throw Error("Error: malformed BAM record at decompressed offset " + std::to_string(dec_off + p) + " of " + rd.what);
+      if (dec.size() - p < 4ull + bs) break;
+      read_length = bam_record_single_match((const uint8_t*)dec.data() + p, bs);
+      p += 4ull + bs;
+    }
+    dec.erase(0, p);
+    dec_off += p;
+  }
+  if (!have_header) throw Error("Error: truncated BAM header in " + rd.what);
+}
+
 // ---- the arithmetic of Profile::train behind the counting (Profile.cpp:1471-1483) ----
 struct Model {
   std::string bases;
@@ -486,13 +663,33 @@ void run(const simu_train_options& o, simu_train_stats& st) {
   }
   tfirst[key_of_row.size()] = tspos.size();
   // ---- Profile::init (Profile.cpp:172-218): the read length is the first single-nM CIGAR of the text ----
+  const bool decode_bam = o.decode_bam != 0;
   LineSource src;
-  src.open(o);
-  std::unique_ptr<ChunkReader> rd(new ChunkReader(eng.ctx, src.fp, o.threads));
+  std::unique_ptr<ChunkReader> rd;
+  std::unique_ptr<BamReader> brd;
+  BamHeader bam_header;
+  std::vector<std::string> replay;   // (standard input: the batches the header and the read length took)
   int cur = 0;
-  bool have = rd->fill(cur);
+  bool have = false;
   int read_length = 0;
-  {
+  if (decode_bam) {
+    brd.reset(new BamReader(eng.ctx, o.bam ? o.bam : "", o.threads));
+    src.what = brd->what;
+    if (brd->fd >= 0) {   // a file shows its end now; a pipe once it is read
+      if (brd->size >= 28) {
+        brd->last28.resize(28);
+        if (pread(brd->fd, &brd->last28[0], 28, (off_t)(brd->size - 28)) != 28) brd->last28.clear();
+      }
+      if (!brd->eof_marker()) std::cerr << "[W::bam_hdr_read] EOF marker is absent. The input is probably truncated" << std::endl;
+    }
+    bam_prepare(eng.ctx, *brd, bam_header, read_length, replay);
+    if (brd->fd >= 0) brd->rewind();
+  } else {
+    src.open(o);
+    rd.reset(new ChunkReader(eng.ctx, src.fp, o.threads));
+    have = rd->fill(cur);
+  }
+  if (!decode_bam) {
     const char* p = rd->buf[cur];
     const char* end = p + rd->len[cur];
     while (p < end && !read_length) {
@@ -528,6 +725,34 @@ void run(const simu_train_options& o, simu_train_stats& st) {
     if (rc == SG_ERR_INVALID && m.find("malformed read") != std::string::npos) throw Error(m, 1);
     throw Error(std::string("GPU engine error in ") + where + ": " + m);
   };
+  if (decode_bam) {
+    std::vector<const char*> names;
+    for (const std::string& n : bam_header.names) names.push_back(n.c_str());
+    eng.check(sg_train_bam_start(eng.ctx, names.data(), (uint32_t)names.size(), bam_header.bytes), "sg_train_bam_start");
+    for (const std::string& b : replay) {
+      if (sg_train_capped(eng.ctx)) break;
+      engine_said(sg_train_feed_bgzf(eng.ctx, b.data(), b.size()), "sg_train_feed_bgzf");
+      st.bam_bytes += b.size();
+    }
+    replay.clear();
+    bool more = !sg_train_capped(eng.ctx) && brd->fill(cur);
+    while (more) {
+      bool next = false;
+      std::string reader_error;
+      std::thread reader([&]() { try { next = brd->fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
+      const int rc = sg_train_feed_bgzf(eng.ctx, brd->buf[cur], brd->len[cur]);
+      reader.join();
+      engine_said(rc, "sg_train_feed_bgzf");
+      if (!reader_error.empty()) throw Error(reader_error);
+      st.bam_bytes += brd->len[cur];
+      cur ^= 1;
+      more = next && !sg_train_capped(eng.ctx);
+    }
+    if (!sg_train_capped(eng.ctx)) engine_said(sg_train_feed_bgzf(eng.ctx, nullptr, 0), "sg_train_feed_bgzf");
+    if (brd->fd < 0 && !brd->eof_marker() && !sg_train_capped(eng.ctx))
+      std::cerr << "[W::bam_hdr_read] EOF marker is absent. The input is probably truncated" << std::endl;
+    eng.check(sg_train_bam_info(eng.ctx, &st.bam_records, nullptr, &st.t_inflate), "sg_train_bam_info");
+  }
   while (have) {
     // the next chunk is read while the device works on this one
     bool more = false;
@@ -561,6 +786,7 @@ void run(const simu_train_options& o, simu_train_stats& st) {
   }
   st.t_reads = since(t1);
   rd.reset();
+  brd.reset();
   src.close();
   if (C.isize_overflow || C.indel_len_overflow)
     throw Error("Error: insert sizes beyond " + std::to_string(kIsizeCols) + " or CIGAR insertions / deletions beyond " + std::to_string(kIndelCols) +

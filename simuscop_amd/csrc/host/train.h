@@ -25,6 +25,8 @@ typedef struct simu_train_options {
   const char* stamp;      // NULL: the current time as saveResults prints it; tests pass a fixed line
   uint64_t max_reads;     // --max-reads (additive): Profile::processRead's maxCount; 0 = the reference's 300,000,000 counted reads
                           // (600,000,000 with targets), behind which it stops reading (Profile.cpp:236, 497-507)
+  int32_t decode_bam;     // --decode-bam (additive): `bam` is read and decoded here (BGZF inflate and the records on the GPU) instead
+                          // of through samtools; the lines are the ones `samtools view -F 0xD04 -q 20` prints
 } simu_train_options;
 
 typedef struct simu_train_stats {
@@ -32,6 +34,8 @@ typedef struct simu_train_stats {
   int32_t read_length, bins, gc_fitted, capped;   // capped: the run ended at max_reads
   double t_reference, t_reads, t_total;   // seconds: reference to the device; SAM text through the kernels; everything
   double insert_rate, del_rate, std_isize, gc_std;
+  uint64_t bam_bytes, bam_records;   // --decode-bam: BGZF bytes fed, records decoded (kept or not)
+  double t_inflate;                  // seconds in sg_train_feed_bgzf (inflate, record boundaries, rendering)
 } simu_train_stats;
 
 void simu_train_default_options(simu_train_options* o);

@@ -2,6 +2,8 @@
 // same options, same checks, same exit codes) over the GPU path of host/train.cpp.
 // Additive options the reference would reject:
 //   --sam <file|->   lines of `samtools view -F 0xD04 -q 20` text from a file or standard input (instead of running samtools)
+//   --decode-bam     with -b: the BAM file is read here -- BGZF inflated and the records decoded on the GPU -- instead of through
+//                    `samtools view -F 0xD04 -q 20` (same lines, no samtools needed; -s is ignored)
 //   --max-reads <n>  Profile::processRead's cap on counted reads (default: the reference's 300,000,000; twice that with targets)
 //   --device <n>     GPU to use (default 0)        --quiet   no progress lines        --stats   one JSON line of counts and times
 #include <getopt.h>
@@ -27,6 +29,7 @@ static void usage(const char* app) {
             << "    -k, --kmer <int>                the length of kmer sequence [default:3]\n"
             << "    -B, --bins <int>                the number of bins into which bases of read are grouped [default:50]\n"
             << "        --sam <file|->              (GPU build) reads as `samtools view` text from a file or standard input\n"
+            << "        --decode-bam                (GPU build) with -b: decode the BAM file on the GPU instead of running samtools\n"
             << "        --device <int>              (GPU build) device to use [default:0]\n"
             << "        --quiet                     (GPU build) no progress lines\n"
             << "        --max-reads <int>           (GPU build) stop at so many counted reads [default: the reference's 300000000,\n"
@@ -46,6 +49,7 @@ int main(int argc, char* argv[]) {
       {"vcf", required_argument, 0, 'v'},   {"ref", required_argument, 0, 'r'},    {"output", required_argument, 0, 'o'},
       {"samtools", required_argument, 0, 's'}, {"kmer", required_argument, 0, 'k'}, {"bins", required_argument, 0, 'B'},
       {"sam", required_argument, 0, 1000},  {"device", required_argument, 0, 1001}, {"quiet", no_argument, 0, 1002},   {"stats", no_argument, 0, 1003},      {"max-reads", required_argument, 0, 1004},
+      {"decode-bam", no_argument, 0, 1005},
       {0, 0, 0, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "hb:t:v:r:o:s:k:B:", long_options, NULL)) != -1) {
@@ -64,8 +68,17 @@ int main(int argc, char* argv[]) {
       case 1002: o.quiet = 1; break;
       case 1003: stats = true; break;
       case 1004: o.max_reads = strtoull(optarg, nullptr, 10); break;
+      case 1005: o.decode_bam = 1; break;
       default: usage(argv[0]); return 1;
     }
+  }
+  if (o.decode_bam && bam.empty()) {
+    std::cerr << "Error: --decode-bam needs a BAM file: use --bam to specify it." << std::endl;
+    return 1;
+  }
+  if (o.decode_bam && !sam.empty()) {
+    std::cerr << "Error: --decode-bam and --sam cannot be used together." << std::endl;
+    return 1;
   }
   if (bam.empty() && sam.empty()) {
     std::cerr << "Use --bam to specify a normal BAM file." << std::endl;
@@ -82,7 +95,7 @@ int main(int argc, char* argv[]) {
     usage(argv[0]);
     return 1;
   }
-  if (samtools.empty() && sam.empty()) {
+  if (samtools.empty() && sam.empty() && !o.decode_bam) {
     std::cerr << "\nWarning: the path of samtools not specified!" << std::endl;
     std::cerr << "Assume the tool has been installed and included in the system PATH!" << std::endl;
   }
@@ -103,12 +116,17 @@ int main(int argc, char* argv[]) {
     if (err[0]) std::cerr << err << std::endl;
     return rc;
   }
-  if (stats)
+  if (stats) {
     fprintf(stderr, "{\"lines\": %llu, \"reads_counted\": %llu, \"gc_rejected\": %llu, \"gc_windows\": %llu, \"gc_pairs\": %llu, \"skipped_overhang\": %llu, "
-                    "\"sam_bytes\": %llu, \"read_length\": %d, \"bins\": %d, \"gc_fitted\": %d, \"capped\": %d, \"t_reference\": %.4f, \"t_reads\": %.4f, \"t_total\": %.4f}\n",
+                    "\"sam_bytes\": %llu, \"read_length\": %d, \"bins\": %d, \"gc_fitted\": %d, \"capped\": %d, \"t_reference\": %.4f, \"t_reads\": %.4f, \"t_total\": %.4f",
             (unsigned long long)st.lines, (unsigned long long)st.reads_counted, (unsigned long long)st.gc_rejected, (unsigned long long)st.gc_windows,
             (unsigned long long)st.gc_pairs, (unsigned long long)st.skipped_overhang, (unsigned long long)st.sam_bytes, st.read_length, st.bins, st.gc_fitted, st.capped,
             st.t_reference, st.t_reads, st.t_total);
+    if (o.decode_bam)   // BGZF bytes fed, records decoded (kept or not), seconds of the decode stage
+      fprintf(stderr, ", \"bam_bytes\": %llu, \"bam_records\": %llu, \"t_inflate\": %.4f", (unsigned long long)st.bam_bytes,
+              (unsigned long long)st.bam_records, st.t_inflate);
+    fprintf(stderr, "}\n");
+  }
   if (!o.quiet) {
     const long secs = (long)st.t_total;
     std::cerr << "\nElapsed time: " << secs / 60 << " minutes and " << secs % 60 << " seconds!\n" << std::endl;

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "sg_bam.h"
 #include "sg_deflate.h"
 #include "sg_train.h"
 #include "sg_device.h"
@@ -260,7 +261,8 @@ struct sg_ctx {
   sg::DevProfile P{};
   sg::DevBatch B{};
   DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_actual, win_namebase, rlen, events, reclen,
-      recoff, meta, totals, bsum, out1, out2, gcw, gco, gcm, slowq, ref_raw, ref_codes, ref_meta, hap_work, gz1, gz2, gz_work;
+      recoff, meta, totals, bsum, out1, out2, gcw, gco, gcm, slowq, ref_raw, ref_codes, ref_meta, hap_work, gz1, gz2, gz_work,
+      infl_src, infl_meta, infl_out, infl_crc;   // sg_inflate_bgzf (infl_crc also serves the training session's BAM input)
   uint64_t gz_bytes[2] = {0, 0};
   bool gz_valid = false;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
@@ -434,7 +436,8 @@ void sg_destroy(sg_ctx* ctx) {
   for (DevBuf* b : {&ctx->tab, &ctx->chains, &ctx->chains2, &ctx->chain_meta, &ctx->windows, &ctx->segmeta, &ctx->prefix, &ctx->pairs,
                     &ctx->win_actual, &ctx->win_namebase, &ctx->rlen, &ctx->events, &ctx->reclen, &ctx->recoff,
                     &ctx->meta, &ctx->totals, &ctx->bsum, &ctx->out1, &ctx->out2, &ctx->gcw, &ctx->gco, &ctx->gcm, &ctx->slowq,
-                    &ctx->ref_raw, &ctx->ref_codes, &ctx->ref_meta, &ctx->hap_work, &ctx->gz1, &ctx->gz2, &ctx->gz_work})
+                    &ctx->ref_raw, &ctx->ref_codes, &ctx->ref_meta, &ctx->hap_work, &ctx->gz1, &ctx->gz2, &ctx->gz_work, &ctx->infl_src,
+                    &ctx->infl_meta, &ctx->infl_out, &ctx->infl_crc})
     b->release();
   for (auto& kv : ctx->wstore) kv.second.release();
   ctx->wplan.release();
@@ -803,10 +806,23 @@ struct sg_train_session {
   uint64_t windows_cap = 0;          // rows the window arrays hold
   sg::TrainCarry* mail = nullptr;    // pinned: the carry a chunk left, the flag word behind it
   uint32_t* mail_flags() { return (uint32_t*)(mail + 1); }
+  // BAM input (sg_train_bam_start, sg_train_feed_bgzf): members are inflated into stream[scur] behind the partial record the
+  // call before left there (bam_carry bytes); the lines of the whole records are rendered into the text buffers above
+  bool bam = false;
+  uint32_t n_ref = 0;
+  uint64_t bam_skip = 0;             // header bytes of the decompressed stream still to be passed over
+  uint64_t bam_carry = 0;
+  uint64_t bam_file_off = 0;         // file offset of the next member
+  uint64_t bam_stream_off = 0;       // offset in the decompressed stream of stream[scur][0]
+  uint64_t bam_records = 0, bam_inflated = 0;
+  double bam_seconds = 0;
+  int scur = 0;
+  DevBuf names, name_off, bgzf_src, bgzf_meta, stream[2], seg, rec, line_len, line_off, bam_scan, bam_totals;
   void release() {
     if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
     for (DevBuf* b : {&keys, &contigs, &counts, &flags, &text[0], &text[1], &line_end, &reads, &gate, &steps, &windows, &window_rc, &carry, &scan_work,
-                      &tgt, &known, &t_ref, &t_alt, &patch, &gc_out})
+                      &tgt, &known, &t_ref, &t_alt, &patch, &gc_out, &names, &name_off, &bgzf_src, &bgzf_meta, &stream[0], &stream[1], &seg, &rec,
+                      &line_len, &line_off, &bam_scan, &bam_totals})
       b->release();
     if (mail) (void)hipHostFree(mail);
     mail = nullptr;
@@ -1054,6 +1070,10 @@ int train_settle(sg_ctx* ctx, sg_train_session* T) {
 }
 }  // namespace
 
+namespace {
+int train_run_chunk(sg_ctx* ctx, sg_train_session* T, uint64_t bytes);
+}
+
 // One chunk of lines. The copy to the device runs on its own stream into the text buffer the previous chunk is not using, so it
 // overlaps that chunk's kernels; the call returns with its own kernels queued (sg_train_capped / the malformed-line error of
 // chunk k are known when chunk k + 1 is fed or sg_train_finish runs).
@@ -1063,7 +1083,6 @@ int sg_train_feed(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes) {
   if (!T) return ctx->fail(SG_ERR_INVALID, "sg_train_feed: call sg_train_begin first");
   if (!sam_bytes || T->capped) return SG_OK;   // (behind the cap: Profile::train has left its loop, Profile.cpp:1461-1464)
   SG_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
   const bool open_end = sam_text[sam_bytes - 1] != '\n';   // a last line without a line break gets one in the device copy
   const uint64_t bytes = sam_bytes + (open_end ? 1 : 0);
   DevBuf& text = T->text[T->fed & 1];
@@ -1074,6 +1093,15 @@ int sg_train_feed(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes) {
   SG_HIP(hipStreamSynchronize(T->copy_stream));   // the caller's buffer is free again when this returns
   if (rc != SG_OK) return rc;
   if (T->capped) return SG_OK;
+  return train_run_chunk(ctx, T, bytes);
+}
+
+namespace {
+// The kernels of one chunk of whole lines that lies in T->text[T->fed & 1] (the chunk before settled).
+int train_run_chunk(sg_ctx* ctx, sg_train_session* T, uint64_t bytes) {
+  hipStream_t s = ctx->stream;
+  DevBuf& text = T->text[T->fed & 1];
+  int rc = SG_OK;
   SG_ENSURE(T->scan_work, sg::train_scan_work_bytes(bytes / 64 + 1));
   sg::TrainJob J;
   train_job(ctx, T, J);
@@ -1123,6 +1151,7 @@ int sg_train_feed(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes) {
   T->fed++;
   return SG_OK;
 }
+}  // namespace
 
 // 1 once the cap on counted reads was reached. A chunk's verdict is known when the next one is fed (or at sg_train_finish):
 // a caller that stops feeding on it has handed over at most one chunk the reference would not have read, which is dropped.
@@ -1203,6 +1232,302 @@ int sg_train_count(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes, const 
   if (rc == SG_OK) rc = sg_train_finish(ctx, out, nullptr, nullptr, 0, nullptr);
   if (rc != SG_OK) sg_train_end(ctx);
   return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// BGZF / BAM input (sg_inflate.hip, sg_bam.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+// The member headers of a buffer (SAMv1 section 4.1): up to `cap` whole members; *whole = bytes they make up.  A member
+// cut by the end of the buffer ends the walk; a header that is not BGZF is an error (message in *err).
+int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap, std::vector<sg::InflateMember>* out, uint64_t* n_out,
+              uint64_t* whole, std::string* err, uint64_t* offs = nullptr, uint32_t* bsizes = nullptr, uint32_t* isizes = nullptr) {
+  uint64_t p = 0, n = 0, dst = 0;
+  auto bad = [&](const char* what) {
+    *err = "BGZF member at file offset " + std::to_string(file_off + p) + ": " + what;
+    *n_out = n;
+    *whole = p;
+    return SG_ERR_INVALID;
+  };
+  while (p < bytes && n < cap) {
+    if (bytes - p < 12) break;
+    if (b[p] != 31 || b[p + 1] != 139 || b[p + 2] != 8 || !(b[p + 3] & 4)) return bad("not a gzip member with an extra field");
+    const uint32_t xlen = b[p + 10] | ((uint32_t)b[p + 11] << 8);
+    if (p + 12 + xlen > bytes) break;
+    int64_t bsize = -1;
+    for (uint64_t q = p + 12; q + 4 <= p + 12 + xlen;) {
+      const uint32_t slen = b[q + 2] | ((uint32_t)b[q + 3] << 8);
+      if (b[q] == 'B' && b[q + 1] == 'C' && slen == 2 && q + 6 <= p + 12 + xlen) { bsize = b[q + 4] | ((uint32_t)b[q + 5] << 8); break; }
+      q += 4 + slen;
+    }
+    if (bsize < 0) return bad("no BC subfield");
+    const uint64_t size = (uint64_t)bsize + 1;
+    if (size < 12 + xlen + 8 || size < sg::kBgzfMinMember - 2) return bad("BSIZE smaller than its own header and trailer");
+    if (p + size > bytes) break;
+    const uint32_t isize = b[p + size - 4] | ((uint32_t)b[p + size - 3] << 8) | ((uint32_t)b[p + size - 2] << 16) | ((uint32_t)b[p + size - 1] << 24);
+    if (isize > sg::kBgzfMaxIsize) return bad("ISIZE above 64 KiB");
+    if (out) out->push_back(sg::InflateMember{p, dst, (uint32_t)size, isize, file_off + p});
+    if (offs) offs[n] = p;
+    if (bsizes) bsizes[n] = (uint32_t)bsize;
+    if (isizes) isizes[n] = isize;
+    dst += isize;
+    n++;
+    p += size;
+  }
+  *n_out = n;
+  *whole = p;
+  return SG_OK;
+}
+
+const char* inflate_verdict(uint32_t v) {
+  static const char* what[] = {"", "block type 3", "over-subscribed, incomplete or unused Huffman code", "distance beyond the output",
+                               "DEFLATE data runs past the member", "more than 64 KiB of output", "ISIZE does not match the output",
+                               "CRC-32 does not match the output", "stored block length does not match its complement", "header longer than the member"};
+  return v < sizeof what / sizeof what[0] ? what[v] : "malformed";
+}
+
+// Members of `src` (already on the device) inflated to d_out + member.dst; the verdicts land in meta behind the member table.
+int inflate_launch(sg_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes, const std::vector<sg::InflateMember>& mem, DevBuf& meta, uint8_t* d_out,
+                   hipStream_t s, hipStream_t copy) {
+  if (!ctx->infl_crc.p) {
+    SG_ENSURE(ctx->infl_crc, (256 + sg::kCrcLevels * 128) * 4);
+    SG_HIP(hipMemcpy(ctx->infl_crc.p, sg::inflate_crc_tab(), 256 * 4, hipMemcpyHostToDevice));
+    SG_HIP(hipMemcpy(ctx->infl_crc.as<uint32_t>() + 256, sg::inflate_crc_shift(), sg::kCrcLevels * 128 * 4, hipMemcpyHostToDevice));
+  }
+  const size_t tab = mem.size() * sizeof(sg::InflateMember);
+  SG_ENSURE(meta, tab + mem.size() * 4 + 64);
+  SG_HIP(hipMemcpyAsync(meta.p, mem.data(), tab, hipMemcpyHostToDevice, copy));
+  SG_HIP(hipStreamSynchronize(copy));
+  sg::InflateJob J;
+  J.src = d_src;
+  J.src_bytes = src_bytes;
+  J.members = meta.as<sg::InflateMember>();
+  J.n = (uint32_t)mem.size();
+  J.out = d_out;
+  J.status = (uint32_t*)(meta.as<uint8_t>() + tab);
+  J.crc_tab = ctx->infl_crc.as<uint32_t>();
+  J.crc_shift = J.crc_tab + 256;
+  sg::launch_inflate(J, s);
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+// the verdicts of inflate_launch (after the stream has been synchronised); the first member that failed names the error
+int inflate_verdicts(sg_ctx* ctx, const std::vector<sg::InflateMember>& mem, const DevBuf& meta, const char* who) {
+  std::vector<uint32_t> st(mem.size());
+  if (mem.empty()) return SG_OK;
+  SG_HIP(hipMemcpy(st.data(), meta.as<uint8_t>() + mem.size() * sizeof(sg::InflateMember), mem.size() * 4, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < mem.size(); i++)
+    if (st[i])
+      return ctx->fail(SG_ERR_INVALID, std::string(who) + ": BGZF member at file offset " + std::to_string(mem[i].file_off) + ": " + inflate_verdict(st[i]));
+  return SG_OK;
+}
+}  // namespace
+
+int sg_bgzf_members(const void* buf, uint64_t bytes, uint64_t* offsets, uint32_t* bsize, uint32_t* isize, uint64_t cap, uint64_t* n_members,
+                    uint64_t* whole_bytes) {
+  if ((bytes && !buf) || !n_members || !whole_bytes) return SG_ERR_INVALID;
+  std::string err;
+  const int rc = bgzf_walk((const uint8_t*)buf, bytes, 0, cap, nullptr, n_members, whole_bytes, &err, offsets, bsize, isize);
+  if (rc != SG_OK) g_create_error = "sg_bgzf_members: " + err;
+  return rc;
+}
+
+int sg_inflate_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes, void* out, uint64_t out_cap, uint64_t* out_bytes) {
+  if (!ctx || (bytes && !members) || !out_bytes) return SG_ERR_INVALID;
+  SG_HIP(hipSetDevice(ctx->device));
+  std::vector<sg::InflateMember> mem;
+  uint64_t n = 0, whole = 0, total = 0;
+  std::string err;
+  if (bgzf_walk((const uint8_t*)members, bytes, 0, ~0ull, &mem, &n, &whole, &err) != SG_OK) return ctx->fail(SG_ERR_INVALID, "sg_inflate_bgzf: " + err);
+  if (whole != bytes)
+    return ctx->fail(SG_ERR_INVALID, "sg_inflate_bgzf: BGZF member at file offset " + std::to_string(whole) + " is cut short by the end of the buffer");
+  for (const sg::InflateMember& m : mem) total += m.isize;
+  *out_bytes = total;
+  if (total > out_cap) return ctx->fail(SG_ERR_OVERFLOW, "sg_inflate_bgzf: the inflated bytes do not fit out_cap");
+  if (!n) return SG_OK;
+  if (!out) return SG_ERR_INVALID;
+  hipStream_t s = ctx->stream;
+  SG_ENSURE(ctx->infl_src, bytes + 64);
+  SG_ENSURE(ctx->infl_out, total + 64);
+  SG_HIP(hipMemcpyAsync(ctx->infl_src.p, members, bytes, hipMemcpyHostToDevice, s));
+  int rc = inflate_launch(ctx, ctx->infl_src.as<uint8_t>(), bytes, mem, ctx->infl_meta, ctx->infl_out.as<uint8_t>(), s, s);
+  if (rc != SG_OK) return rc;
+  SG_HIP(hipStreamSynchronize(s));
+  if ((rc = inflate_verdicts(ctx, mem, ctx->infl_meta, "sg_inflate_bgzf")) != SG_OK) return rc;
+  SG_HIP(hipMemcpy(out, ctx->infl_out.p, total, hipMemcpyDeviceToHost));
+  return SG_OK;
+}
+
+int sg_train_bam_start(sg_ctx* ctx, const char* const* ref_names, uint32_t n_ref, uint64_t first_record_skip) {
+  if (!ctx || (n_ref && !ref_names)) return SG_ERR_INVALID;
+  sg_train_session* T = ctx->train;
+  if (!T) return ctx->fail(SG_ERR_INVALID, "sg_train_bam_start: call sg_train_begin first");
+  if (T->fed || T->bam) return ctx->fail(SG_ERR_INVALID, "sg_train_bam_start: call it once, before anything is fed");
+  SG_HIP(hipSetDevice(ctx->device));
+  std::string names;
+  std::vector<uint64_t> off(n_ref + 1, 0);
+  for (uint32_t i = 0; i < n_ref; i++) {
+    if (!ref_names[i]) return SG_ERR_INVALID;
+    off[i] = names.size();
+    names += ref_names[i];
+    names += '\0';
+  }
+  off[n_ref] = names.size();
+  SG_ENSURE(T->names, names.size() + 64);
+  SG_ENSURE(T->name_off, off.size() * 8 + 64);
+  if (!names.empty()) SG_HIP(hipMemcpy(T->names.p, names.data(), names.size(), hipMemcpyHostToDevice));
+  SG_HIP(hipMemcpy(T->name_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+  SG_ENSURE(T->bam_totals, 64);
+  T->bam = true;
+  T->n_ref = n_ref;
+  T->bam_skip = first_record_skip;
+  return SG_OK;
+}
+
+namespace {
+const char* bam_verdict(uint32_t v) {
+  switch (v) {
+    case sg::kBamShort: return "block_size smaller than its fixed fields";
+    case sg::kBamOpCode: return "CIGAR operation code above 8";
+    case sg::kBamRefId: return "reference id outside the header's list";
+    default: return "l_read_name of 0 or a negative l_seq";
+  }
+}
+}  // namespace
+
+int sg_train_feed_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes) {
+  if (!ctx || (bytes && !members)) return SG_ERR_INVALID;
+  sg_train_session* T = ctx->train;
+  if (!T || !T->bam) return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: call sg_train_begin and sg_train_bam_start first");
+  if (T->capped) return SG_OK;
+  SG_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!bytes) {   // the end of the stream: nothing may be left of a record
+    const int rc = train_settle(ctx, T);
+    if (rc != SG_OK || T->capped) return rc;
+    if (T->bam_carry)
+      return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: the BAM record at decompressed offset " + std::to_string(T->bam_stream_off) +
+                                           " runs past the end of the stream");
+    return SG_OK;
+  }
+  std::vector<sg::InflateMember> mem;
+  uint64_t n = 0, whole = 0, total = 0;
+  std::string err;
+  if (bgzf_walk((const uint8_t*)members, bytes, T->bam_file_off, ~0ull, &mem, &n, &whole, &err) != SG_OK)
+    return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: " + err);
+  if (whole != bytes)
+    return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: BGZF member at file offset " + std::to_string(T->bam_file_off + whole) +
+                                         " is cut short (truncated file?)");
+  const uint64_t carry = T->bam_carry;
+  for (sg::InflateMember& m : mem) { m.dst += carry; total += m.isize; }
+  const uint64_t L = carry + total;
+  // stage the members while the chunk before is still counted
+  SG_ENSURE(T->bgzf_src, bytes + 64);
+  SG_HIP(hipMemcpyAsync(T->bgzf_src.p, members, bytes, hipMemcpyHostToDevice, T->copy_stream));
+  int rc = train_settle(ctx, T);
+  SG_HIP(hipStreamSynchronize(T->copy_stream));   // the caller's buffer is free again when this returns
+  if (rc != SG_OK) return rc;
+  if (T->capped) return SG_OK;
+  DevBuf& S = T->stream[T->scur];
+  if ((rc = grow_keep(ctx, S, carry, L + 64)) != SG_OK) return rc;
+  if ((rc = inflate_launch(ctx, T->bgzf_src.as<uint8_t>(), bytes, mem, T->bgzf_meta, S.as<uint8_t>(), s, T->copy_stream)) != SG_OK) return rc;
+  // ---- record boundaries ----
+  uint64_t base = 0;
+  if (T->bam_skip) {   // (the header: nothing is carried while it lasts)
+    base = std::min(T->bam_skip, L);
+    T->bam_skip -= base;
+  }
+  const uint32_t n_seg = L > base ? (uint32_t)((L - base + sg::kBamSegment - 1) / sg::kBamSegment) : 0;
+  SG_ENSURE(T->seg, (size_t)n_seg * 28 + 64);
+  SG_ENSURE(T->bam_scan, (size_t)(sg::scan_blocks(std::max<uint32_t>(n_seg, 1)) + 1) * 8 + 64);
+  sg::BamJob J;
+  memset(&J, 0, sizeof J);
+  J.d = S.as<uint8_t>();
+  J.base = base;
+  J.L = L;
+  J.n_ref = T->n_ref;
+  J.names = T->names.as<char>();
+  J.name_off = T->name_off.as<uint64_t>();
+  J.n_seg = n_seg;
+  J.guess = T->seg.as<uint64_t>();
+  J.exit = J.guess + n_seg;
+  J.first = J.exit + n_seg;
+  J.count = (uint32_t*)(J.first + n_seg);
+  J.scan_bsum = T->bam_scan.as<uint64_t>();
+  J.totals = T->bam_totals.as<uint64_t>();
+  uint64_t h_tot[4] = {0, 0, base, ~0ull};
+  SG_HIP(hipMemcpyAsync(J.totals, h_tot, 32, hipMemcpyHostToDevice, s));
+  if (n_seg) {
+    sg::launch_bam_guess(J, s);
+    sg::launch_bam_verify(J, s);
+    sg::launch_scan_u32(J.count, n_seg, J.scan_bsum, J.first, J.totals, s);
+  }
+  SG_HIP(hipGetLastError());
+  SG_HIP(hipMemcpyAsync(h_tot, J.totals, 32, hipMemcpyDeviceToHost, s));
+  SG_HIP(hipStreamSynchronize(s));
+  if ((rc = inflate_verdicts(ctx, mem, T->bgzf_meta, "sg_train_feed_bgzf")) != SG_OK) return rc;
+  auto record_error = [&](uint64_t key) {
+    return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: BAM record at decompressed offset " + std::to_string(T->bam_stream_off + (key >> 8)) + ": " +
+                                         bam_verdict((uint32_t)(key & 0xFF)));
+  };
+  if (h_tot[3] != ~0ull) return record_error(h_tot[3]);
+  const uint64_t n_rec = h_tot[0], tail = h_tot[2];
+  uint64_t text_bytes = 0;
+  if (n_rec) {
+    SG_ENSURE(T->rec, n_rec * 8 + 64);
+    SG_ENSURE(T->line_len, n_rec * 4 + 64);
+    SG_ENSURE(T->line_off, n_rec * 8 + 64);
+    SG_ENSURE(T->bam_scan, (size_t)(sg::scan_blocks((uint32_t)n_rec) + 1) * 8 + 64);
+    J.scan_bsum = T->bam_scan.as<uint64_t>();
+    J.rec = T->rec.as<uint64_t>();
+    J.n_rec = n_rec;
+    J.line_len = T->line_len.as<uint32_t>();
+    J.line_off = T->line_off.as<uint64_t>();
+    sg::launch_bam_starts(J, s);
+    sg::launch_bam_measure(J, s);
+    sg::launch_scan_u32(J.line_len, (uint32_t)n_rec, J.scan_bsum, J.line_off, J.totals + 1, s);
+    SG_HIP(hipGetLastError());
+    SG_HIP(hipMemcpyAsync(h_tot, J.totals, 32, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    if (h_tot[3] != ~0ull) return record_error(h_tot[3]);
+    text_bytes = h_tot[1];
+  }
+  if (text_bytes) {
+    DevBuf& text = T->text[T->fed & 1];
+    SG_ENSURE(text, text_bytes + 64);
+    J.text = text.as<char>();
+    sg::launch_bam_render(J, s);
+    SG_HIP(hipGetLastError());
+  }
+  // the partial record behind the last whole one goes to the front of the other stream buffer
+  const uint64_t left = L - tail;
+  DevBuf& N = T->stream[T->scur ^ 1];
+  SG_ENSURE(N, left + 64);
+  if (left) SG_HIP(hipMemcpyAsync(N.p, S.as<uint8_t>() + tail, left, hipMemcpyDeviceToDevice, s));
+  T->scur ^= 1;
+  T->bam_carry = left;
+  T->bam_stream_off += tail;
+  T->bam_file_off += bytes;
+  T->bam_records += n_rec;
+  T->bam_inflated += total;
+  if (text_bytes) {
+    SG_HIP(hipStreamSynchronize(s));
+    T->bam_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return train_run_chunk(ctx, T, text_bytes);
+  }
+  T->bam_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return SG_OK;
+}
+
+int sg_train_bam_info(sg_ctx* ctx, uint64_t* records, uint64_t* inflated_bytes, double* seconds) {
+  if (!ctx) return SG_ERR_INVALID;
+  sg_train_session* T = ctx->train;
+  if (!T || !T->bam) return ctx->fail(SG_ERR_INVALID, "sg_train_bam_info: no BAM input in this session");
+  if (records) *records = T->bam_records;
+  if (inflated_bytes) *inflated_bytes = T->bam_inflated;
+  if (seconds) *seconds = T->bam_seconds;
+  return SG_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

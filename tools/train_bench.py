@@ -2,7 +2,10 @@
 contig (40x, XTen PE) become `samtools view` lines sorted by position; K contigs chr1..chrK of that one sequence and K copies
 of the lines (contig field rewritten) make a text of K x 250 MB.  Prints the --stats line of `seqToProfile` and GB/s of SAM
 text through the kernels; with `rocprofv3 --kernel-trace --stats -- python3 tools/train_bench.py` the per-kernel times.
-usage: python tools/train_bench.py [K=8] [workdir]"""
+--bam: the same reads written as BAM (tests/bam_util.py, BGZF members of 65,280 bytes at zlib levels 1 and 6) and read by
+`seqToProfile -b x.bam --decode-bam` (BGZF inflate, record boundaries and rendering on the GPU): compressed GB/s and records/s
+end to end, next to the --sam figures, and the profile checked against the --sam one.
+usage: python tools/train_bench.py [--bam] [K=8] [workdir]"""
 import json
 import os
 import subprocess
@@ -17,8 +20,10 @@ import cases  # noqa: E402
 import histo_util as H  # noqa: E402
 import train_util as TU  # noqa: E402
 
-K = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-wd = sys.argv[2] if len(sys.argv) > 2 else tempfile.mkdtemp(prefix="trainbench_")
+BAM = "--bam" in sys.argv
+ARGS = [a for a in sys.argv[1:] if a != "--bam"]
+K = int(ARGS[0]) if len(ARGS) > 0 else 8
+wd = ARGS[1] if len(ARGS) > 1 else tempfile.mkdtemp(prefix="trainbench_")
 os.makedirs(wd, exist_ok=True)
 SIMU = os.path.join(ROOT, "simuscop_amd", "lib", "simuReads")
 EXE = os.path.join(ROOT, "simuscop_amd", "lib", "seqToProfile")
@@ -52,3 +57,66 @@ for rep in range(3):
     if best is None or st["t_reads"] < best["t_reads"]:
         best = st
 print(json.dumps(best))
+if not BAM:
+    sys.exit(0)
+
+
+def _bgzf_part(args):
+    import bam_util as B
+    data, level = args
+    return b"".join(B.bgzf_member(data[i:i + 65280], level) for i in range(0, len(data), 65280))
+
+
+def write_bam(path, level):
+    """The lines of reads.sam as a BAM: chr1's records encoded once, copies for chr2..chrK with refID / next_refID patched."""
+    import multiprocessing
+    import numpy as np
+    import bam_util as B
+    sam = open(sam_path, "rb").read()
+    one = [ln for ln in sam.split(b"\n") if ln and ln.split(b"\t", 3)[2] == b"chr1"]
+    seq_len = len(open(fa_path, "rb").read().split(b">chr2")[0].split(b"\n", 1)[1].replace(b"\n", b""))
+    refs = [(b"chr%d" % k, seq_len) for k in range(1, K + 1)]
+    ref_id = {n: i for i, (n, _) in enumerate(refs)}
+    recs = [B.record(ln.split(b"\t"), ref_id) for ln in one]
+    offs = np.cumsum([0] + [len(r) for r in recs[:-1]])
+    base = np.frombuffer(b"".join(recs), np.uint8)
+    mate = base[offs + 24] != 0xFF
+    parts = [B.header(refs, b"@HD\tVN:1.6\n")]
+    for k in range(K):
+        a = base.copy()
+        a[offs + 4] = k
+        a[offs[mate] + 24] = k
+        parts.append(a.tobytes())
+    data = b"".join(parts)
+    step = 65280 * 256
+    with multiprocessing.Pool(16) as pool:
+        blobs = pool.map(_bgzf_part, [(data[i:i + step], level) for i in range(0, len(data), step)])
+    with open(path, "wb") as f:
+        f.write(b"".join(blobs) + B.EOF_MEMBER)
+    return len(data)
+
+
+want_body = open(os.path.join(wd, "out.profile"), "rb").read().split(b"\n", 2)[2]
+for level in (1, 6):
+    bam = os.path.join(wd, "reads_l%d.bam" % level)
+    if not os.path.exists(bam):
+        t0 = time.time()
+        raw = write_bam(bam, level)
+        print("BAM level %d made in %.1f s: %d bytes inflated, %d compressed" % (level, time.time() - t0, raw, os.path.getsize(bam)), file=sys.stderr)
+    bb = None
+    for rep in range(3):
+        out = os.path.join(wd, "bam_l%d.profile" % level)
+        r = subprocess.run([EXE, "-b", bam, "--decode-bam", "-v", vcf_path, "-r", fa_path, "-o", out, "--quiet", "--stats"],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert open(out, "rb").read().split(b"\n", 2)[2] == want_body, "profile differs from the --sam route"
+        st = json.loads(r.stderr.strip().split("\n")[-1])
+        assert st["lines"] == best["lines"] and st["reads_counted"] == best["reads_counted"]
+        st["level"] = level
+        st["bam_GBps_end_to_end"] = st["bam_bytes"] / st["t_reads"] / 1e9
+        st["records_per_s_end_to_end"] = st["bam_records"] / st["t_reads"]
+        st["bam_GBps_decode_stage"] = st["bam_bytes"] / st["t_inflate"] / 1e9
+        st["sam_lines_per_s_same_reads"] = best["lines_per_s"]
+        if bb is None or st["t_reads"] < bb["t_reads"]:
+            bb = st
+    print(json.dumps(bb))
