@@ -1,0 +1,110 @@
+// sg_api.h -- what the two files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
+// sink, reference, haplotypes, window planner) and sg_api_train.cpp (profile training, BGZF / BAM input).  Internal: the
+// ABI itself is include/simuscop_amd.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "sg_device.h"
+#include "sg_haplotypes.h"
+
+// A grow-only device buffer that owns its block.  The block goes back to the process's block cache (sg_api.cpp) when the
+// buffer is destroyed, released or assigned over; the cache waits for the device first, so nothing still queued can touch
+// the block once it is handed out again.  Move-only: a move hands the block over.
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  int dev = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)), dev(o.dev) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { release(); p = std::exchange(o.p, nullptr); cap = std::exchange(o.cap, 0); dev = o.dev; }
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  int ensure(size_t bytes);   // at least `bytes` (contents not kept); 0 or the hipError_t of the failed allocation
+  void release();
+  template <class T> T* as() const { return (T*)p; }
+};
+
+extern thread_local std::string g_create_error;   // sg_last_error(nullptr): calls without a context
+
+struct sg_outputs;
+struct sg_train_session;
+
+struct sg_ctx {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  uint64_t seed = 0;
+  std::string err;
+
+  bool have_profile = false, have_haps = false, have_plan = false, sampled = false;
+  sg::DevProfile P{};
+  sg::DevBatch B{};
+  DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_actual, win_namebase, events, recoff, meta, totals, bsum,
+      out1, out2, gcw, gco, gcm, slowq, ref_raw, ref_codes, ref_meta, hap_work, gz1, gz2, gz_work,
+      infl_src, infl_meta, infl_out, infl_crc;   // sg_inflate_bgzf (infl_crc also serves the training session's BAM input)
+  // the haplotype chains in `chains` (sg_upload_haplotypes, sg_build_haplotypes): chain c holds len[c] bases from off[c] on;
+  // chain_meta holds the same on the device for the kernels, the host checks against this copy
+  struct ChainLayout {
+    std::vector<uint64_t> off, len;
+    size_t total = 0;   // bytes of the padded chains buffer
+  } hap;
+  uint64_t gz_bytes[2] = {0, 0};
+  bool gz_valid = false;
+  std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
+  // device-made sampling plan: window weights per store id (sg_windows_build), the batch table of sg_plan_windows
+  std::map<uint32_t, DevBuf> wstore;
+  std::map<uint32_t, uint64_t> wstore_n;
+  DevBuf wplan, wwork;
+  struct PlanInfo {
+    bool valid = false;
+    uint64_t n_windows = 0;
+    uint32_t n_active = 0, batch_id = 0;
+    int32_t paired = 0;
+    std::string prefix;
+    std::vector<uint32_t> seg_first, seg_size;  // per active segment (seg_first has n_active + 1 entries)
+    std::vector<uint64_t> slot_first;           // planned fragments before each active segment; [n_active] = total
+  } winfo;
+  uint64_t ref_raw_bytes = 0;
+  sg_train_session* train = nullptr;   // profile training in progress (sg_train_begin .. sg_train_finish / sg_train_end)
+  std::vector<sg::DevContig> ref_contigs;  // host copy of the committed contig table
+  uint64_t host_totals[4] = {0, 0, 0, 0};
+  uint64_t host_flags[2] = {0, 0};  // totals[3..4] after the emit kernels: flags, slow-queue counts
+  uint64_t* mail = nullptr;         // pinned: where a pass's totals[0..4] land (copied to the two arrays above by finish_pass)
+  bool pass_pending = false;        // a pass is queued whose totals have not been looked at yet
+  bool speculative = false;         // ... and its emit kernels were launched before the text size was known (see run_pass)
+  uint64_t slow_items = 0;
+  bool slow_overflow = false;
+  bool results_valid = false;
+
+  bool profiling = false;
+  hipEvent_t evs[8] = {};  // 0-3 starts of plan..scan, 4 end of scan, 5 start of emit, 6 end of emit, 7 between the two emit kernels
+  bool evs_created = false;
+  float last_ms[SG_K_COUNT] = {0, 0, 0, 0, 0, 0};
+
+  ~sg_ctx();   // streams, events, pinned mail and spare output sets; the buffers go with their members
+  int fail(int code, const std::string& m) { err = m; return code; }
+  int hipfail(hipError_t e, const char* what) {
+    err = std::string(what) + ": " + hipGetErrorString(e);
+    return SG_ERR_HIP;
+  }
+};
+
+#define SG_HIP(call)                                        \
+  do {                                                      \
+    hipError_t _e = (call);                                 \
+    if (_e != hipSuccess) return ctx->hipfail(_e, #call);   \
+  } while (0)
+#define SG_ENSURE(buf, bytes)                                                                  \
+  do {                                                                                         \
+    int _e = (buf).ensure(bytes);                                                              \
+    if (_e) return ctx->hipfail((hipError_t)_e, "hipMalloc(" #buf ")");                        \
+  } while (0)

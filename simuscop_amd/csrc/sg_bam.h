@@ -63,7 +63,5 @@ void launch_bam_verify(const BamJob& J, hipStream_t s);    // exit[b - 1] == ent
 void launch_bam_starts(const BamJob& J, hipStream_t s);    // (after the scan of count) every record start
 void launch_bam_measure(const BamJob& J, hipStream_t s);   // filter, check, rendered length
 void launch_bam_render(const BamJob& J, hipStream_t s);    // (after the scan of line_len) the eleven fields as text
-void launch_scan_u32(const uint32_t* in, uint32_t n, uint64_t* bsum, uint64_t* out, uint64_t* total, hipStream_t s);
-uint32_t scan_blocks(uint32_t n);
 
 }  // namespace sg

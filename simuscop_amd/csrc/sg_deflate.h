@@ -11,6 +11,8 @@
 // here from a token histogram of 512 members spread over the text.  The device kernels (sg_deflate.hip) find the matches,
 // look codes up, pack bits and compute CRC-32s.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
 #include <vector>
 
@@ -65,5 +67,32 @@ uint32_t crc_advance(const DeflatePlan& plan, uint32_t state, uint64_t n);
 inline uint32_t member_bytes(const DeflatePlan& p, uint64_t data_bits) {
   return (uint32_t)((p.prefix_bits + data_bits + p.lit_len[256] + 7) / 8 + 8);
 }
+
+// ---- device side (sg_deflate.hip): the job of the three kernels ----
+struct DevDeflate {
+  const uint8_t* text;
+  uint64_t bytes;
+  uint32_t n_chunks;
+  const uint32_t* code;       // [288] literal/length: reversed code | length << 16
+  const uint32_t* len_tok;    // [68] length code + extra bits of a match length | bits << 24
+  const uint32_t* dist_code;  // [32] reversed code | length << 16
+  const uint32_t* prefix;     // member prefix words (BSIZE = 0)
+  uint32_t prefix_words, prefix_bits;
+  const uint32_t* crc_tab;    // [4][256]
+  const uint32_t* crc_shift;  // [kGzLevels][8][16]
+  uint32_t crc_init_full, crc_init_last;
+  uint32_t* next;             // [2] chunk counters of the match / encode kernels (zeroed by the host)
+  uint32_t* msize;            // [n_chunks] member bytes
+  const uint64_t* moff;       // [n_chunks] member offsets
+  uint4* rec;                 // [n_chunks * 512 * 2] token records
+  uint32_t* lbits;            // [n_chunks * 512] bits of a lane's tokens | bytes its last match takes over from the next lanes << 10
+  unsigned long long* hist;   // [320] literal/length counts, then distance counts at 288
+  uint8_t* out;
+  uint32_t min_run;           // shortest match taken at distance 1 (kGzMinRun)
+  uint32_t min_copy;          // shortest copy taken from the table (kGzMinGramMatch)
+};
+void launch_gz_hist(const DevDeflate& D, uint32_t n_chunks, hipStream_t s);     // token histogram of the sampled members
+void launch_gz_match(const DevDeflate& D, uint32_t n_chunks, hipStream_t s);    // tokens -> records, bits per lane, member sizes
+void launch_gz_encode(const DevDeflate& D, uint32_t n_chunks, uint32_t prefix_bits, hipStream_t s);   // the members
 
 }  // namespace sg

@@ -30,29 +30,6 @@
 
 namespace sg {
 
-struct DevDeflate {
-  const uint8_t* text;
-  uint64_t bytes;
-  uint32_t n_chunks;
-  const uint32_t* code;       // [288] literal/length: reversed code | length << 16
-  const uint32_t* len_tok;    // [68] length code + extra bits of a match length | bits << 24
-  const uint32_t* dist_code;  // [32] reversed code | length << 16
-  const uint32_t* prefix;     // member prefix words (BSIZE = 0)
-  uint32_t prefix_words, prefix_bits;
-  const uint32_t* crc_tab;    // [4][256]
-  const uint32_t* crc_shift;  // [kGzLevels][8][16]
-  uint32_t crc_init_full, crc_init_last;
-  uint32_t* next;             // [2] chunk counters of the match / encode kernels (zeroed by the host)
-  uint32_t* msize;            // [n_chunks] member bytes
-  const uint64_t* moff;       // [n_chunks] member offsets
-  uint4* rec;                 // [n_chunks * 512 * 2] token records
-  uint32_t* lbits;            // [n_chunks * 512] bits of a lane's tokens | bytes its last match takes over from the next lanes << 10
-  unsigned long long* hist;   // [320] literal/length counts, then distance counts at 288
-  uint8_t* out;
-  uint32_t min_run;           // shortest match taken at distance 1 (kGzMinRun)
-  uint32_t min_copy;          // shortest copy taken from the table (kGzMinGramMatch)
-};
-
 constexpr uint32_t kGzTab = 1u << kGzHashBits;
 // members sampled for the token histogram: every stride-th, at most kGzSamples of them
 __host__ __device__ inline uint32_t gz_sample_stride(uint32_t n_chunks) { return (n_chunks + kGzSamples - 1u) / kGzSamples; }
@@ -671,31 +648,31 @@ __global__ __launch_bounds__(kGzThreads) void gz_encode_kernel(DevDeflate D, uin
 
 // ---- launchers -------------------------------------------------------------------------------------
 static size_t gz_token_lds() { return ((size_t)kGzTab + 4 + 288 + kGzLenTokens + 32 + 8 + 64 + 64) * 4 + kGzChunk + kGzTxtPad; }
-void launch_gz_hist(const void* d, uint32_t n_chunks, hipStream_t s) {
+void launch_gz_hist(const DevDeflate& D, uint32_t n_chunks, hipStream_t s) {
   if (!n_chunks) return;
   const size_t lds = gz_token_lds();
   (void)hipFuncSetAttribute((const void*)gz_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const uint32_t stride = gz_sample_stride(n_chunks);
   const uint32_t grid = (n_chunks + stride - 1u) / stride;  // <= kGzSamples: one workgroup each, one round on 256 CUs
-  hipLaunchKernelGGL(gz_hist_kernel, dim3(grid), dim3(kGzThreads), lds, s, *(const DevDeflate*)d);
+  hipLaunchKernelGGL(gz_hist_kernel, dim3(grid), dim3(kGzThreads), lds, s, D);
 }
 uint32_t gz_stage_words(uint32_t prefix_bits) {  // worst case: 15 bits per byte (a match token is <= 48 bits for >= 4 bytes)
   return ((prefix_bits + 15u * kGzChunk + 15u + 7u) / 8u + 8u + 3u) / 4u + 4u;
 }
-void launch_gz_match(const void* d, uint32_t n_chunks, hipStream_t s) {
+void launch_gz_match(const DevDeflate& D, uint32_t n_chunks, hipStream_t s) {
   if (!n_chunks) return;
   const size_t lds = gz_token_lds();
   (void)hipFuncSetAttribute((const void*)gz_match_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const uint32_t grid = n_chunks < 512u ? n_chunks : 512u;  // two workgroups per CU fit in LDS
-  hipLaunchKernelGGL(gz_match_kernel, dim3(grid), dim3(kGzThreads), lds, s, *(const DevDeflate*)d);
+  hipLaunchKernelGGL(gz_match_kernel, dim3(grid), dim3(kGzThreads), lds, s, D);
 }
-void launch_gz_encode(const void* d, uint32_t n_chunks, uint32_t prefix_bits, hipStream_t s) {
+void launch_gz_encode(const DevDeflate& D, uint32_t n_chunks, uint32_t prefix_bits, hipStream_t s) {
   if (!n_chunks) return;
   const uint32_t sw = gz_stage_words(prefix_bits);
   const size_t lds = ((size_t)sw + 288 + kGzLenTokens + 32 + 1024 + kGzLevels * 128 + kGzThreads + 8) * 4;
   (void)hipFuncSetAttribute((const void*)gz_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const uint32_t grid = n_chunks < 512u ? n_chunks : 512u;  // two workgroups per CU fit in LDS
-  hipLaunchKernelGGL(gz_encode_kernel, dim3(grid), dim3(kGzThreads), lds, s, *(const DevDeflate*)d, sw);
+  hipLaunchKernelGGL(gz_encode_kernel, dim3(grid), dim3(kGzThreads), lds, s, D, sw);
 }
 
 }  // namespace sg

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "simuscop_amd.h"
+#include "sg_haplotypes.h"
 
 namespace sg {
 
@@ -57,15 +58,7 @@ __global__ __launch_bounds__(256) void ref_scan_kernel(const uint8_t* __restrict
   }
 }
 
-// ---- contig ingest: raw FASTA lines of fixed width -> base codes ---------------------------------
-struct DevContig {
-  uint64_t raw_off;    // first base in the raw buffer
-  uint64_t code_off;   // first code in the encoded reference
-  uint64_t length;     // bases
-  uint32_t line_bases, line_width;
-  uint64_t first_block;  // exclusive prefix of 16-base blocks over the contigs
-};
-
+// ---- contig ingest: raw FASTA lines of fixed width -> base codes (DevContig) --------------------
 // lane = 16 consecutive bases of one contig.  Line structure is verified on the way: a line break
 // byte that is not '\n' / '\r', or a line break byte inside a line, sets flag 2 (the host then falls
 // back to its general parser).  An image without line ends (line_width == line_bases: what the general
@@ -142,9 +135,7 @@ __global__ __launch_bounds__(256) void ref_ingest_kernel(const uint8_t* __restri
   }
 }
 
-// ---- haplotype assembly ---------------------------------------------------------------------------
-struct DevPiece { uint64_t dst; uint64_t src; uint32_t len; uint32_t pad; };  // absolute byte offsets
-
+// ---- haplotype assembly (DevPiece, DevPatch) ------------------------------------------------------
 // workgroup per piece (the host splits long pieces): aligned 16-byte stores, unaligned 16-byte loads
 __global__ __launch_bounds__(256) void hap_copy_kernel(uint8_t* __restrict__ chains, const uint8_t* __restrict__ ref_codes,
                                                        const uint8_t* __restrict__ literals, const DevPiece* __restrict__ pieces,
@@ -171,7 +162,6 @@ __global__ __launch_bounds__(256) void hap_copy_kernel(uint8_t* __restrict__ cha
   }
 }
 
-struct DevPatch { uint64_t dst; uint32_t base; uint32_t pad; };
 __global__ __launch_bounds__(256) void hap_patch_kernel(uint8_t* __restrict__ chains, const DevPatch* __restrict__ patches, uint64_t n) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
     chains[patches[i].dst] = (uint8_t)encode_base(patches[i].base);
@@ -223,20 +213,18 @@ static uint32_t grid_for(uint64_t items, uint32_t per_block, uint32_t max_blocks
 void launch_ref_scan(const uint8_t* raw, uint64_t n, uint64_t* list, uint32_t cap, uint32_t* count, uint32_t* flags, hipStream_t s) {
   hipLaunchKernelGGL(ref_scan_kernel, dim3(grid_for((n + 15) / 16, 256, 256 * 32)), dim3(256), 0, s, raw, n, list, cap, count, flags);
 }
-void launch_ref_ingest(const uint8_t* raw, uint8_t* codes, const void* contigs, uint32_t n_contigs, uint64_t n_blocks,
+void launch_ref_ingest(const uint8_t* raw, uint8_t* codes, const DevContig* contigs, uint32_t n_contigs, uint64_t n_blocks,
                        uint32_t* flags, hipStream_t s) {
   if (!n_blocks) return;
-  hipLaunchKernelGGL(ref_ingest_kernel, dim3(grid_for(n_blocks, 256, 256 * 64)), dim3(256), 0, s, raw, codes,
-                     (const DevContig*)contigs, n_contigs, n_blocks, flags);
+  hipLaunchKernelGGL(ref_ingest_kernel, dim3(grid_for(n_blocks, 256, 256 * 64)), dim3(256), 0, s, raw, codes, contigs, n_contigs, n_blocks, flags);
 }
-void launch_hap_copy(uint8_t* chains, const uint8_t* ref_codes, const uint8_t* literals, const void* pieces, uint64_t n, hipStream_t s) {
+void launch_hap_copy(uint8_t* chains, const uint8_t* ref_codes, const uint8_t* literals, const DevPiece* pieces, uint64_t n, hipStream_t s) {
   if (!n) return;
-  hipLaunchKernelGGL(hap_copy_kernel, dim3(grid_for(n, 1, 256 * 64)), dim3(256), 0, s, chains, ref_codes, literals,
-                     (const DevPiece*)pieces, n);
+  hipLaunchKernelGGL(hap_copy_kernel, dim3(grid_for(n, 1, 256 * 64)), dim3(256), 0, s, chains, ref_codes, literals, pieces, n);
 }
-void launch_hap_patch(uint8_t* chains, const void* patches, uint64_t n, hipStream_t s) {
+void launch_hap_patch(uint8_t* chains, const DevPatch* patches, uint64_t n, hipStream_t s) {
   if (!n) return;
-  hipLaunchKernelGGL(hap_patch_kernel, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, chains, (const DevPatch*)patches, n);
+  hipLaunchKernelGGL(hap_patch_kernel, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, chains, patches, n);
 }
 void launch_pack2(const uint8_t* chains, uint64_t bytes, uint32_t* fwd2, uint32_t* rc2, uint16_t* bad, hipStream_t s) {  // bytes % 1024 == 0
   const uint64_t n16 = bytes / 16;

@@ -2325,7 +2325,7 @@ __global__ __launch_bounds__(256) void slice_kernel(const sg_window* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers (called from sg_api.cpp through plain C++ declarations)
+// launchers (declared in sg_device.h)
 // ------------------------------------------------------------------------------------------------
 // a pass's sizes and flags (totals[0..4]) to the context's pinned mailbox: a kernel of five lanes writing host memory
 // reaches the host sooner than a copy command of 40 bytes through the DMA engine
@@ -2348,7 +2348,6 @@ void launch_indel(const DevProfile& P, const DevBatch& B, hipStream_t s) {
   if (!B.n_slots) return;
   hipLaunchKernelGGL(indel_kernel, dim3((B.n_slots + 255) / 256), dim3(256), 0, s, P, B);
 }
-bool emit_uses_fast_kernel(const DevProfile& P, const DevBatch& B);
 void launch_header(const DevProfile& P, const DevBatch& B, hipStream_t s) {
   if (!B.n_slots) return;
   const bool fast = emit_uses_fast_kernel(P, B);

@@ -522,6 +522,47 @@ def test_a_chunks_verdict_arrives_with_the_next_call(tmp_path):
             eng.sg_destroy(ctx)
 
 
+def test_a_failed_begin_leaves_no_session(oracle_lib, tmp_path):
+    """sg_train_begin builds its session aside and hands it to the context only when all of it stands.  Six-base contexts
+    and 2^24 bins ask for several TB of counters: hipMalloc refuses before any kernel is launched, begin returns SG_ERR_HIP,
+    a call that needs a session is then refused for the call order, and an ordinary begin / feed / finish on the same
+    context counts what the restatement counts."""
+    import random
+    from simuscop_amd import synth
+    oracle_lib.orc_train_count.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32,
+                                           C.POINTER(simuscop_amd.SgTrainCounts)]
+    wd = str(tmp_path)
+    fa = os.path.join(wd, "r.fa")
+    seq = synth.synth_contig(6000, 5, 0, n_runs=False).tobytes()
+    open(fa, "wb").write(b">chr1\n" + b"".join(seq[i:i + 60] + b"\n" for i in range(0, len(seq), 60)))
+    rng = random.Random(7)
+    sam = b"\n".join(TU._crafted(rng, b"chr1", seq, p, 50, 200) for p in range(1, 5000, 5)) + b"\n"
+    want, wa = TU.count_arrays(simuscop_amd.SgTrainCounts, 84, 10, 1024)
+    assert oracle_lib.orc_train_count(sam, len(sam), fa.encode(), b"ACTG", 3, 10, 1024, 256, C.byref(want)) == 0
+    assert want.reads_counted > 500
+    eng = simuscop_amd.load_engine()
+    ctx = C.c_void_p()
+    assert eng.sg_create(C.byref(ctx), 0, 1) == 0
+    try:
+        keys = _reference_on_device(eng, ctx, fa)
+        karr = (C.c_char_p * len(keys))(*keys)
+        st = simuscop_amd.SgTrainSetup(contig_keys=karr, n_contigs=len(keys), bases=b"ACTG", kmer=6, bins=1 << 24, n_isize=1024, n_indel_len=256,
+                                       count_gc=0, window=1000)
+        assert eng.sg_train_begin(ctx, C.byref(st)) == 2, eng.sg_last_error(ctx)   # SG_ERR_HIP
+        assert b"hipMalloc" in eng.sg_last_error(ctx)
+        names = (C.c_char_p * 1)(b"chr1")
+        assert eng.sg_train_bam_start(ctx, names, 1, 0) == 1   # SG_ERR_INVALID
+        assert b"call sg_train_begin first" in eng.sg_last_error(ctx)
+        st.kmer, st.bins = 3, 10
+        got, ga = TU.count_arrays(simuscop_amd.SgTrainCounts, 84, 10, 1024)
+        assert eng.sg_train_begin(ctx, C.byref(st)) == 0, eng.sg_last_error(ctx)
+        assert eng.sg_train_feed(ctx, sam, len(sam)) == 0, eng.sg_last_error(ctx)
+        assert eng.sg_train_finish(ctx, C.byref(got), None, None, 0, None) == 0, eng.sg_last_error(ctx)
+        _same_counts(got, ga, want, wa)
+    finally:
+        eng.sg_destroy(ctx)
+
+
 @pytest.mark.parametrize("exome", [False, True])
 def test_device_training_stops_at_the_cap(exome, oracle_lib, tmp_path):
     """Profile::processRead's cap on counted reads (Profile.cpp:236, 497-507; twice it with targets) with small values: the
