@@ -330,7 +330,9 @@ int sg_emit_info(sg_ctx* ctx, uint64_t* queued_items, int* requeued);
  *                    Profile::processRead has been reached, further chunks are ignored, as the reference stops reading).
  *                    The text is copied before the call returns (the caller's buffer is free again); the chunk's kernels
  *                    are left running, so its verdict -- SG_ERR_INVALID for a line with fewer than 11 fields
- *                    (Profile.cpp:246-251), the cap -- is reported by the NEXT sg_train_feed or by sg_train_finish
+ *                    (Profile.cpp:246-251), the cap -- is reported by the NEXT sg_train_feed or by sg_train_finish.
+ *                    A chunk that does not end in a line break holds the file's last line, which loses its last
+ *                    character as fgets + `buf[strlen(buf)-1] = '\0'` chop it (Profile.cpp:1458-1459)
  *   sg_train_finish  the count matrices; the (GC content, read count) pairs countGC pushed, in its order (gcs, readCounts)
  * Where the reference's behaviour is undefined the line is skipped and counted: reads hanging over their contig's end
  * (skipped_overhang).  Arrays are the caller's: subs1 / subs2 [kmer_count][bins][4], kmers [bins][kmer_count], quality

@@ -63,8 +63,8 @@ int orc_predict_philox(const orc_profile*, const char* ref, int n, int is_read1,
 
 // ---- profile training (Profile::train, Profile.cpp:1442-1484): see train_oracle.cpp ----
 // Caller-allocated count arrays: subs1/subs2 [kmer_count][bins][N], kmers [bins][kmer_count], quality [N*N][bins][94],
-// isize [n_isize], ins_len / del_len [n_indel_len] (same layout as sg_train_counts).  PARITY UNPINNED for the counting
-// (no samtools / BAM in this image): restated from the source, not run against it.
+// isize [n_isize], ins_len / del_len [n_indel_len] (same layout as sg_train_counts).  Pinned to the
+// unmodified reference seqToProfile by tests/test_train_vs_reference.py (.profile and .gc byte for byte).
 typedef struct orc_train_counts {
   uint64_t *subs1, *subs2, *kmers, *quality, *isize, *ins_len, *del_len;
   uint64_t lines, reads_counted, cigar_chars, insert_events, delete_events, isize_overflow, indel_len_overflow, skipped_overhang,

@@ -7,12 +7,13 @@
 // (:443-450) and the per-(bin, reference x read base, quality) counts (:452-480).  It is the checker of
 // sg_train_count (include/simuscop_amd.h).
 //
-// PARITY UNPINNED.  The reference reads its input through popen("samtools view ...") (Profile.cpp:1448-1449) and
-// neither samtools nor a BAM file exists in this image, so this restatement cannot be run against the reference
-// binary; it follows the source line by line instead.  What a reference run CAN pin is pinned: the unmodified binary
-// loads the profile files written from these counts (Profile::load, :934-1238) and simulates from them exactly as
-// oracle(mt) does (tests/test_trained_profile_vs_reference.py), and the tests hold the counts against the profile
-// tables the reads were sampled from.
+// Pinned to the reference: tests/test_train_vs_reference.py runs the unmodified seqToProfile (built by `make -C oracle
+// ref`) on the tests' SAM text -- tests/stub_samtools.sh stands in for the popen("samtools view ...") of
+// Profile.cpp:135 and :1448 -- and holds the .profile and .gc files orc_train_profile writes to it byte for byte (its
+// recorded runs, tests/golden/reference_train_runs.json, where the binary is not built).  The inputs stay clear of
+// where the reference is undefined (tests/train_util.py: reference_undefined).  The unmodified simulator also loads the
+// profile files written from these counts and samples from them exactly as oracle(mt) does
+// (tests/test_train_profile_cpu.py).
 //
 // orc_train restates the whole of Profile::train (:1442-1484): processRead with Profile::countGC (:512-703) as the
 // sequential state machine it is, the known variants of the VCF (lib/vcfparser/vcfparser.cpp:26-106,
@@ -22,16 +23,20 @@
 //   * reads hanging over the end of their contig: the reference indexes refSeq past its end (:458 with n =
 //     strlen(readSeq)); the line is skipped after its CIGAR walk (`skipped_overhang`).  Reads that START behind the end
 //     (std::string::substr throws in the reference) or lie on an empty contig never reach countGC.
-//   * estimateGCParas thins its samples with `int *curCount = new int[bins]`, never initialised (:735, read at :739):
-//     zero-initialised here.  `gcs[i]*bins` reaches `bins` itself for a window of G/C only (:720,738: one element past
-//     the arrays): the arrays have bins + 1 cells.  `counts[i]/expectCount` divides by zero with fewer than 50 windows
+//   * estimateGCParas thins its samples with `int *curCount = new int[bins]`, never initialised (:735, read at :739).
+//     The allocator hands it the block of `counts`, freed at :728, so the reference's counter of GC bin j starts at
+//     counts[j]; the first 16 bytes hold the free list's link (bins 0-1: an address) and its cleared key (bins 2-3: 0).
+//     Here bins 2 and up start as the reference's do, bins 0-1 at zero (the same as long as fewer than two
+//     expectCounts of windows have a GC content below 0.04: their step is 1 then).  `gcs[i]*bins` reaches `bins` itself
+//     for a window of G/C only (:720,738: one element past the arrays): the arrays have bins + 1 cells.  `counts[i]/expectCount` divides by zero with fewer than 50 windows
 //     (:723-726): the step is 1 then.  The median of no windows (:1473) is 0.
 //     With no GC percent holding more than 20 windows the tails are extrapolated from gcMeans[-1] (:815-820): all means
 //     stay 0 then.
 //   * normParas(false) reads iSizeDist past its row when five times the most frequent insert size exceeds the largest
 //     one seen (:884-889): columns past the row count as 0.
 //   * SNVs outside their contig (written past the string, Genome.cpp:471-474) are skipped.
-//   * an alternative allele that is no letter of ACGTN never equals a read base here (the product compares base codes).
+//   * (not undefined) an alternative allele that is no letter of ACGTN is compared with the read as a character, as
+//     the reference does (:408, :466); the product keeps such an allele's character as its code.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -497,7 +502,8 @@ struct TrainState : Trainer {
     const char* end = sam_text + sam_bytes;
     while (p < end) {
       const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
-      const char* le = nl ? nl : end;
+      // a last line without a line break loses its last character: `buf[strlen(buf)-1] = '\0'` (:1459)
+      const char* le = nl ? nl : end - 1;
       if (stopped) return 0;                            // (Profile::train left its loop, :1461-1464)
       const int ret = processRead(string(p, le));
       if (ret == 1) return 1;
@@ -544,7 +550,8 @@ struct TrainState : Trainer {
     for (int i = 0; i <= gbins; i++) steps[i] = expectCount > 0 ? std::max(1, counts[i] / expectCount) : 1;
     std::ofstream ofs(gcFile.c_str());
     std::vector<int> indxs;
-    std::vector<int> curCount(gbins + 1, 0);
+    std::vector<int> curCount(counts);                   // the reused block of `counts` (:728, :735)
+    for (int j = 0; j < 4; j++) curCount[j] = 0;         // the free list's link and key
     const double med_rc = median(readCounts);
     for (size_t i = 0; i < readCounts.size(); i++) {
       const int j = (int)(gcs[i] * gbins);

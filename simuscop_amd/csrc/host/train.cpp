@@ -453,12 +453,16 @@ double median_of(std::vector<double> v) {   // lib/mydefine/MyDefine.h:72-104; n
 
 // Profile::estimateGCParas (Profile.cpp:713-834): thin the windows to ~150,000, normalise the read counts by their median,
 // fit a locally weighted line at every GC percent.  Four places where the reference reads memory it does not own are
-// given a meaning here: the thinning counters start at zero, a window of G/C only has a cell of its
-// own, fewer than 50 windows thin nothing, and without any fitted percent no tail is extrapolated.
+// given a meaning here: the thinning counters start where the reference's do in practice -- its
+// `new int[bins]` (:735) gets the block of the per-bin counts freed at :728, so bin b starts at per_bin[b], except for
+// bins 0-3, whose first 16 bytes hold the allocator's free-list link and cleared key (zero here) -- a window of G/C only
+// has a cell of its own, fewer than 50 windows thin nothing, and without any fitted percent no tail is extrapolated.
 void fit_gc_model(Model& M, const std::string& gc_file) {
   const int B = 50;
-  std::vector<int> per_bin(B + 1, 0), step(B + 1, 1), seen(B + 1, 0);
+  std::vector<int> per_bin(B + 1, 0), step(B + 1, 1);
   for (double g : M.gcs) per_bin[(int)(g * B)]++;
+  std::vector<int> seen(per_bin);
+  for (int b = 0; b < 4; b++) seen[b] = 0;
   const int expect = std::min(150000, (int)M.gcs.size()) / B;
   if (expect > 0)
     for (int b = 0; b <= B; b++) step[b] = std::max(1, per_bin[b] / expect);

@@ -225,7 +225,7 @@ int sg_train_begin(sg_ctx* ctx, const sg_train_setup* st) {
       uint8_t* d_ch = T->patch.as<uint8_t>() + off.size() * 8;
       SG_HIP(hipMemcpyAsync(T->patch.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
       SG_HIP(hipMemcpyAsync(d_ch, ch.data(), ch.size(), hipMemcpyHostToDevice, s));
-      sg::launch_train_patch((which ? T->t_ref : T->t_alt).as<uint8_t>(), T->patch.as<uint64_t>(), d_ch, off.size(), s);
+      sg::launch_train_patch((which ? T->t_ref : T->t_alt).as<uint8_t>(), T->patch.as<uint64_t>(), d_ch, off.size(), which == 0, s);
       SG_HIP(hipGetLastError());
       SG_HIP(hipStreamSynchronize(s));
     }
@@ -357,12 +357,14 @@ int sg_train_feed(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes) {
   if (!T) return ctx->fail(SG_ERR_INVALID, "sg_train_feed: call sg_train_begin first");
   if (!sam_bytes || T->capped) return SG_OK;   // (behind the cap: Profile::train has left its loop, Profile.cpp:1461-1464)
   SG_HIP(hipSetDevice(ctx->device));
-  const bool open_end = sam_text[sam_bytes - 1] != '\n';   // a last line without a line break gets one in the device copy
-  const uint64_t bytes = sam_bytes + (open_end ? 1 : 0);
+  // A last line without a line break loses its last character, as Profile::train's `buf[strlen(buf)-1] = '\0'` chops it
+  // (Profile.cpp:1459): in the device copy that character becomes the line break.
+  const bool open_end = sam_text[sam_bytes - 1] != '\n';
+  const uint64_t bytes = sam_bytes;
   DevBuf& text = T->text[T->fed & 1];
   SG_ENSURE(text, bytes + 64);
   SG_HIP(hipMemcpyAsync(text.p, sam_text, sam_bytes, hipMemcpyHostToDevice, T->copy_stream));
-  if (open_end) SG_HIP(hipMemsetAsync(text.as<char>() + sam_bytes, '\n', 1, T->copy_stream));
+  if (open_end) SG_HIP(hipMemsetAsync(text.as<char>() + sam_bytes - 1, '\n', 1, T->copy_stream));
   int rc = train_settle(ctx, T);
   SG_HIP(hipStreamSynchronize(T->copy_stream));   // the caller's buffer is free again when this returns
   if (rc != SG_OK) return rc;

@@ -87,6 +87,6 @@ void launch_train_lines_fill(const TrainJob& J, hipStream_t s);    // ... -> lin
 void launch_train_chunk(const TrainJob& J, hipStream_t s);      // everything else of one chunk (needs n_lines)
 void launch_train_window_gc(const TrainWindow* w, const uint32_t* rc, uint64_t n, const TrainContig* contigs, const uint8_t* ref_codes,
                             uint32_t wes, double* gc, double* rcs, hipStream_t s);
-void launch_train_patch(uint8_t* codes, const uint64_t* off, const uint8_t* ch, uint64_t n, hipStream_t s);
+void launch_train_patch(uint8_t* codes, const uint64_t* off, const uint8_t* ch, uint64_t n, bool keep_other, hipStream_t s);
 
 }  // namespace sg

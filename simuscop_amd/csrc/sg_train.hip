@@ -512,7 +512,7 @@ __device__ __forceinline__ void count_base(const TrainJob& J, const TrainRead& R
         bool eq;
         if (ac <= 3u) eq = c == "ACTG"[ac];
         else eq = rev ? !(c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'a' || c == 'c' || c == 'g' || c == 't')   // (both complement to 'N')
-                      : (ac == 4u && c == 'N');
+                      : (ac == 4u ? c == 'N' : (uint32_t)(uint8_t)c == ac);   // (an allele of no base: its own character)
         if (eq) { code = ac; *is_alt = true; }
       }
     }
@@ -677,13 +677,16 @@ __global__ __launch_bounds__(256) void train_window_gc_kernel(const TrainWindow*
   }
 }
 
-__global__ __launch_bounds__(256) void train_patch_kernel(uint8_t* codes, const uint64_t* off, const uint8_t* ch, uint64_t n) {
+// keep_other (the altSequence table): an allele that is no letter of ACGTN keeps its upper-case character as its code, so the
+// read can be compared with it as the reference compares characters (Profile.cpp:408, :466); every code above 3 is no base.
+__global__ __launch_bounds__(256) void train_patch_kernel(uint8_t* codes, const uint64_t* off, const uint8_t* ch, uint64_t n, bool keep_other) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t b = ch[i];
   if (b >= 'a' && b <= 'z') b -= 32u;   // Genome.cpp:529-530
   const bool acgt = (b == 'A') | (b == 'C') | (b == 'G') | (b == 'T');
-  codes[off[i]] = (uint8_t)(acgt ? ((b >> 1) & 3u) : (b == 'N' ? 4u : (b == 'X' ? 6u : 5u)));
+  const uint32_t other = keep_other && b > 6u ? b : (b == 'X' ? 6u : 5u);
+  codes[off[i]] = (uint8_t)(acgt ? ((b >> 1) & 3u) : (b == 'N' ? 4u : other));
 }
 
 }  // namespace
@@ -733,9 +736,9 @@ void launch_train_window_gc(const TrainWindow* w, const uint32_t* rc, uint64_t n
   hipLaunchKernelGGL(train_window_gc_kernel, dim3(grid), dim3(256), 0, s, w, rc, n, contigs, ref_codes, wes, gc, rcs);
 }
 
-void launch_train_patch(uint8_t* codes, const uint64_t* off, const uint8_t* ch, uint64_t n, hipStream_t s) {
+void launch_train_patch(uint8_t* codes, const uint64_t* off, const uint8_t* ch, uint64_t n, bool keep_other, hipStream_t s) {
   if (!n) return;
-  hipLaunchKernelGGL(train_patch_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, codes, off, ch, n);
+  hipLaunchKernelGGL(train_patch_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, codes, off, ch, n, keep_other);
 }
 
 }  // namespace sg

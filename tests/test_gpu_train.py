@@ -2,9 +2,11 @@
 `seqToProfile` command line against the CPU restatement of Profile::train (oracle/train_oracle.cpp), on SAM lines made from
 reads THE GPU sampled plus crafted lines (every filter, the CIGAR walk, known variants, several contigs, reads that step
 backwards, exome targets).  Bar: every counter and every (GC, read count) pair bit-exact, the written profile byte for byte
-(integer work, then the same fp64 operations in the same order).  The counting is PARITY UNPINNED against the reference
-binary (no samtools / BAM here); what a reference run can pin is pinned: the unmodified binary loads the file `seqToProfile`
-wrote and samples from it exactly as oracle(mt) does (below, and tests/test_train_profile_cpu.py on the CPU)."""
+(integer work, then the same fp64 operations in the same order).  The restatement is held to the unmodified reference
+seqToProfile by tests/test_train_vs_reference.py, and the product directly by tests/test_gpu_train_vs_reference.py; the
+unmodified simulator loads the file `seqToProfile` wrote and samples from it exactly as oracle(mt) does (below, and
+tests/test_train_profile_cpu.py on the CPU).  The crafted lines include a read that starts behind its contig's end, on
+which the reference aborts (Genome.cpp:435): here it pins the product's own choice."""
 import ctypes as C
 import os
 import subprocess

@@ -1,7 +1,7 @@
 """Profile training, counting half on the CPU: the restatement of Profile::processRead's counters
-(oracle/train_oracle.cpp) applied to SAM lines made from reads the oracle itself sampled.  PARITY UNPINNED -- no samtools,
-no BAM in this image, so the restatement is not run against the reference binary -- but the loop closes: normalised, the
-counts must give back the profile tables the reads were drawn from (the inverse of Profile::predict)."""
+(oracle/train_oracle.cpp) applied to SAM lines made from reads the oracle itself sampled: normalised, the counts must give
+back the profile tables the reads were drawn from (the inverse of Profile::predict).  The restatement itself is held to the
+unmodified reference seqToProfile by tests/test_train_vs_reference.py."""
 import ctypes as C
 import os
 

@@ -1,9 +1,13 @@
 """Profile training end to end on the CPU: the restatement of Profile::train (oracle/train_oracle.cpp:
 processRead with countGC, known variants, targets, estimateGCParas, normParas(false), saveResults) on reads the oracle
-sampled, and the ONE pin a reference run can give it here (no samtools, no BAM: the counting stays "parity unpinned"):
-the unmodified reference binary LOADS the profile file written from those counts (Profile::load, Profile.cpp:934-1238) and
-simulates from it exactly as oracle(mt) does.  tests/test_gpu_train.py holds the GPU path (the product: `seqToProfile`,
-sg_train_*) against this restatement, byte for byte."""
+sampled: the unmodified reference simulator LOADS the profile file written from those counts (Profile::load,
+Profile.cpp:934-1238) and simulates from it exactly as oracle(mt) does.  tests/test_train_vs_reference.py holds the files
+themselves to the unmodified reference seqToProfile; tests/test_gpu_train.py holds the GPU path (the product:
+`seqToProfile`, sg_train_*) against this restatement, byte for byte.
+
+The `trained` input keeps a read that starts behind chr1's end and one that hangs over it.  On the first the reference
+aborts (std::out_of_range from substr, Genome.cpp:435), on the second it reads past its copies of the contig
+(Profile.cpp:457-461): these tests pin the product's own choice there (train_oracle.cpp's header)."""
 import ctypes as C
 import hashlib
 import os

@@ -165,3 +165,119 @@ def training_inputs(wd, fa_one, sim_lines, L, exome=False, seed=5):
     out.append(_crafted(rng, b"chr1", chr1, len(chr1) + 5, L, 300))                      # starts behind it
     out += filter_lines(L)
     return fa, vcf_path, bed_path, b"\n".join(out) + b"\n"
+
+
+# ---- where the unmodified reference seqToProfile is undefined (tests/test_train_vs_reference.py stays out of it) ----
+def abbr_of_chr(name):
+    """MyDefine.cpp:212-225: what follows "chrom", else what follows "chr", else the name."""
+    i = name.find(b"chrom")
+    if i >= 0:
+        return name[i + 5:]
+    i = name.find(b"chr")
+    return name[i + 3:] if i >= 0 else name
+
+
+def fasta_lengths(fa):
+    """{abbreviated contig name: length} of a FASTA file (first token of the header line)."""
+    out, name = {}, None
+    for line in open(fa, "rb"):
+        line = line.rstrip(b"\r\n")
+        if line.startswith(b">"):
+            name = abbr_of_chr(line[1:].split()[0])
+            out[name] = 0
+        elif name is not None:
+            out[name] += len(line)
+    return out
+
+
+def kmer_count(k):
+    """Contexts of length k, with the 'X' that stands before the read's first base (Profile::initKmers)."""
+    return sum(4 ** m for m in range(1, k + 1))
+
+
+def reference_undefined(lib, fa, vcf, bed, sam):
+    """Why the reference seqToProfile's output is undefined on this input: one line per cause found, none when it is
+    defined.  Each cause is named with the line that makes it so; the product makes a stated choice there
+    (oracle/train_oracle.cpp's header), which a reference run cannot pin:
+
+      * a read that starts behind its contig's end: `refSequence.substr` throws (Genome.cpp:435, called at
+        Profile.cpp:384) and the reference aborts;
+      * a read that hangs over its contig's end: the quality loop runs to strlen(readSeq) over the shorter copies refSeq
+        and altSeq and reads past their end (Profile.cpp:457-461);
+      * a known SNV behind its contig's end: Genome::generateChrSequence writes past the sequence (Genome.cpp:471-474);
+      * normParas(false) reads iSizeDist past its row when five times the most frequent insert size exceeds the
+        largest one counted (Profile.cpp:869-889);
+      * no GC window at all: the median of an empty vector reads p[-1] (Profile.cpp:1473, MyDefine.h:75-80);
+      * with the GC model fitted (median read count 5 or more, Profile.cpp:1475): a window of G/C only indexes one past
+        counts / curCount (:720-721, :738-739); fewer than 50 windows make expectCount 0, and :726 divides by it; bins 0
+        and 1 (GC below 0.04) of the never initialised curCount (:735) start at the allocator's free-list link, which
+        matters when more than two expectCounts of windows fall in them (their step is above 1, :726, :739).
+
+    Lines are checked on their text alone, whether or not an earlier filter would drop them (the stricter reading).  The
+    windows and the insert sizes come from the restatement's counters (`lib`: liboracle), whose windows the tests pin to
+    the reference's .gc file."""
+    import ctypes as C
+    import simuscop_amd
+    out = []
+    lens = fasta_lengths(fa)
+    for ln in sam.split(b"\n"):
+        f = ln.split(b"\t")
+        if len(f) < 11 or f[9] == b"*" or abbr_of_chr(f[2]) not in lens or not f[3].isdigit() or int(f[3]) == 0:
+            continue
+        start, n, end = int(f[3]) - 1, len(f[9]), lens[abbr_of_chr(f[2])]
+        if start > end:
+            out.append(b"starts behind its contig (Genome.cpp:435): " + ln[:60])
+        elif start + n > end:
+            out.append(b"hangs over its contig's end (Profile.cpp:457-461): " + ln[:60])
+    for ln in open(vcf, "rb"):
+        f = ln.split(b"\t")
+        if ln.startswith(b"#") or len(f) < 5 or abbr_of_chr(f[0]) not in lens:
+            continue
+        if len(f[3]) == 1 and len(f[4]) == 1 and int(f[1]) > lens[abbr_of_chr(f[0])]:
+            out.append(b"known SNV behind its contig (Genome.cpp:471-474): " + ln[:60])
+    n_isize = 1 << 16
+    st, a = count_arrays(simuscop_amd.SgTrainCounts, kmer_count(3), 50, n_isize)
+    cap = 1 << 20
+    gc, rc, n = (C.c_double * cap)(), (C.c_double * cap)(), C.c_uint64()
+    rcode = lib.orc_train(sam, len(sam), fa.encode(), vcf.encode(), (bed or "").encode(), b"ACTG", 3, 50, n_isize, 256, C.byref(st), gc, rc, cap,
+                          C.byref(n))
+    assert rcode == 0
+    isz = a["isize"]
+    mode = int(np.argmax(isz)) if isz.any() else 0           # the first of the most frequent (strict >, :870-875)
+    cols = max(10, n_isize + 1 if st.isize_overflow else (int(np.flatnonzero(isz)[-1]) + 1 if isz.any() else 0))
+    if 5 * mode > cols:
+        out.append(b"five times the modal insert size %d passes the largest counted one (Profile.cpp:878-889)" % mode)
+    g, r = np.array(gc[:n.value]), np.array(rc[:n.value])
+    if not len(g):
+        out.append(b"no GC window (Profile.cpp:1473, MyDefine.h:75-80)")
+    elif np.median(r) >= 5:
+        if (g >= 1).any():
+            out.append(b"a window of G/C only (Profile.cpp:720-721)")
+        if len(g) < 50:
+            out.append(b"fewer than 50 windows with the GC model fitted (Profile.cpp:723-726)")
+        else:
+            expect = min(150000, len(g)) // 50
+            for b in (0, 1):
+                if ((g * 50).astype(int) == b).sum() >= 2 * expect:
+                    out.append(b"GC bin %d thinned from the allocator's link (Profile.cpp:735-739)" % b)
+    return out
+
+
+def defined_lines(lines, lens):
+    """`lines` without those that start behind or hang over their contig's end (see reference_undefined)."""
+    keep = []
+    for ln in lines:
+        f = ln.split(b"\t")
+        c = abbr_of_chr(f[2]) if len(f) > 3 else None
+        if len(f) >= 11 and c in lens and f[3].isdigit() and int(f[3]) > 0 and f[9] != b"*" and int(f[3]) - 1 + len(f[9]) > lens[c]:
+            continue
+        keep.append(ln)
+    return keep
+
+
+def wide_insert_line(line, tlen=2500):
+    """A copy of SAM line `line` (a read that is counted) with TLEN `tlen`: it widens iSizeDist past five modal insert sizes
+    (Profile.cpp:446-450, 869-889) when put right behind it."""
+    f = line.split(b"\t")
+    f[0], f[1], f[8] = b"wide", b"0", b"%d" % tlen
+    return b"\t".join(f)
