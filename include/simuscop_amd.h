@@ -408,6 +408,25 @@ int sg_train_bam_info(sg_ctx* ctx, uint64_t* records, uint64_t* inflated_bytes, 
 /* Which emit kernel the loaded profile gets (after sg_load_profile): 0 generic (tables that do not fit
  * LDS, k-mer sizes other than 3), 1 straight-line kernel (table image in LDS). */
 int sg_emit_variant(sg_ctx* ctx);
+/* The emit kernels the last pass launched (after sg_result), read-only.  main_kernel: SG_EMIT_STRAIGHT_LINE (k-mer 3, the
+ * table image in LDS; the items it queues go to emit_slow_kernel), SG_EMIT_GENERIC_K3_LDS (generic kernel specialised for
+ * k-mer 3, substitution rows staged in LDS), SG_EMIT_GENERIC_LDS (generic kernel, any k-mer, rows in LDS),
+ * SG_EMIT_GENERIC_GLOBAL (generic kernel, rows read from global memory: contexts x bins x 16 bytes do not fit beside the
+ * read rows).  slow_rows_lds: 1 / 0 when emit_slow_kernel stages its rows in LDS / reads them from global memory, -1
+ * without the straight-line kernel.  lds_bytes: dynamic LDS of the main kernel.  clean_cap: per-wave entries of the
+ * straight-line kernel's list of one-indel reads' clean items (0: those reads stay whole in the general steps).
+ * A pass whose item queue overflowed (sg_emit_info) was emitted again by the generic kernel on top of this. */
+#define SG_EMIT_STRAIGHT_LINE 1
+#define SG_EMIT_GENERIC_K3_LDS 2
+#define SG_EMIT_GENERIC_LDS 3
+#define SG_EMIT_GENERIC_GLOBAL 4
+typedef struct sg_emit_path_info {
+  int32_t main_kernel;
+  int32_t slow_rows_lds;
+  uint32_t lds_bytes;
+  uint32_t clean_cap;
+} sg_emit_path_info;
+int sg_emit_path(const sg_ctx* ctx, sg_emit_path_info* info);
 
 /* Exact u32 form of the reference's inverse-CDF draw, exposed for tests: number of 32-bit draws
  * x for which randIndx's `r <= c` holds (r = 2.2204e-16 + (1-2.2204e-16)*x/2^32).               */

@@ -25,7 +25,7 @@ ENGINE_SYMBOLS = [
     "sg_reference_commit", "sg_build_haplotypes", "sg_haplotype_codes", "sg_compress", "sg_fetch_compressed",
     "sg_bgzf_eof", "sg_deflate_plan", "sg_detach_outputs", "sg_outputs_sizes", "sg_outputs_fetch",
     "sg_outputs_last_error", "sg_release_outputs", "sg_plan", "sg_sample", "sg_result", "sg_fetch", "sg_device_output",
-    "sg_gc_percent", "sg_set_profiling", "sg_kernel_times", "sg_emit_info", "sg_emit_variant", "sg_cdf_count_le", "sg_fetch_range", "sg_host_alloc",
+    "sg_gc_percent", "sg_set_profiling", "sg_kernel_times", "sg_emit_info", "sg_emit_variant", "sg_emit_path", "sg_cdf_count_le", "sg_fetch_range", "sg_host_alloc",
     "sg_sub_row_identity_first", "sg_row_symbols", "sg_alias_row", "sg_window_weights", "sg_windows_build", "sg_plan_windows", "sg_plan_range", "sg_windows_drop",
     "sg_host_free", "sg_profile_prepare", "sg_profile_tables_error", "sg_load_prepared_profile", "sg_profile_tables_free", "sg_train_count",
     "sg_train_begin", "sg_train_feed", "sg_train_capped", "sg_train_finish", "sg_train_end",
@@ -108,6 +108,11 @@ class SimuOptions(C.Structure):
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32)
 
 
+class SgEmitPathInfo(C.Structure):
+    """sg_emit_path_info (include/simuscop_amd.h)"""
+    _fields_ = [("main_kernel", C.c_int32), ("slow_rows_lds", C.c_int32), ("lds_bytes", C.c_uint32), ("clean_cap", C.c_uint32)]
+
+
 class SimuStats(C.Structure):
     _fields_ = [("reads", C.c_uint64), ("fragments", C.c_uint64), ("fastq_bytes", C.c_uint64),
                 ("planned_reads", C.c_uint64), ("windows", C.c_uint64), ("segments", C.c_uint64),
@@ -115,7 +120,9 @@ class SimuStats(C.Structure):
                 ("t_plan", C.c_double), ("t_sample", C.c_double), ("t_fetch", C.c_double),
                 ("t_write", C.c_double), ("t_total", C.c_double), ("kernel_ms", C.c_float * 8),
                 ("queued_items", C.c_uint64), ("requeued_batches", C.c_uint64), ("t_engine", C.c_double),
-                ("t_reference", C.c_double), ("t_hap_device", C.c_double), ("t_plan_api", C.c_double), ("t_compress", C.c_double), ("gz_bytes", C.c_uint64)]
+                ("t_reference", C.c_double), ("t_hap_device", C.c_double), ("t_plan_api", C.c_double), ("t_compress", C.c_double), ("gz_bytes", C.c_uint64),
+                ("emit_kernel", C.c_int32), ("emit_slow_rows_lds", C.c_int32), ("emit_lds_bytes", C.c_uint32),
+                ("emit_clean_cap", C.c_uint32)]
 
 
 _engine = None
@@ -190,6 +197,7 @@ def load_engine():
     lib.sg_kernel_times.argtypes = [vp, C.POINTER(C.c_float)]
     lib.sg_emit_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     lib.sg_emit_variant.argtypes = [vp]
+    lib.sg_emit_path.argtypes = [vp, C.POINTER(SgEmitPathInfo)]
     lib.sg_cdf_count_le.argtypes = [C.c_double]
     lib.sg_cdf_count_le.restype = C.c_uint64
     lib.sg_sub_row_identity_first.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]

@@ -518,6 +518,13 @@ struct Driver {
       sg_emit_info(eng.ctx, &queued, &requeued);
       st.queued_items += queued;
       st.requeued_batches += (uint64_t)requeued;
+      sg_emit_path_info path;
+      if (sg_emit_path(eng.ctx, &path) == SG_OK) {
+        st.emit_kernel = path.main_kernel;
+        st.emit_slow_rows_lds = path.slow_rows_lds;
+        st.emit_lds_bytes = path.lds_bytes;
+        st.emit_clean_cap = path.clean_cap;
+      }
     }
     st.t_sample += since(t0);
     st.fragments += nf;

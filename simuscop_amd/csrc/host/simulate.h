@@ -63,6 +63,9 @@ typedef struct simu_stats {
   double t_plan_api;       // part of t_sample: sg_plan calls (window upload, work buffers)
   double t_compress;       // sg_compress calls (gzip mode)
   uint64_t gz_bytes;       // compressed bytes produced (gzip mode)
+  int32_t emit_kernel;     // the emit kernels of the last pass (sg_emit_path: SG_EMIT_*; 0: no pass ran)
+  int32_t emit_slow_rows_lds;
+  uint32_t emit_lds_bytes, emit_clean_cap;
 } simu_stats;
 
 // Returns 0 on success.  On failure returns the exit code the reference would use and writes the

@@ -1129,6 +1129,7 @@ static int launch_text(sg_ctx* ctx, bool prof) {
   }
   if (prof) SG_HIP(hipEventRecord(ctx->evs[5], s));  // after the (first-pass) output allocation
   sg::launch_header(ctx->P, B, s);
+  ctx->emit_path = sg::emit_path(ctx->P, B, false);
   sg::launch_emit(ctx->P, B, s, false, prof ? ctx->evs[7] : nullptr);
   if (prof) SG_HIP(hipEventRecord(ctx->evs[6], s));
   return SG_OK;
@@ -1216,6 +1217,15 @@ static int finish_pass(sg_ctx* ctx) {
 int sg_emit_variant(sg_ctx* ctx) {
   if (!ctx || !ctx->have_profile) return -1;
   return sg::emit_variant(ctx->P);
+}
+
+int sg_emit_path(const sg_ctx* ctx, sg_emit_path_info* info) {
+  if (!ctx || !info || !ctx->results_valid) return SG_ERR_INVALID;
+  info->main_kernel = ctx->emit_path.main_kernel;
+  info->slow_rows_lds = ctx->emit_path.slow_rows_lds;
+  info->lds_bytes = ctx->emit_path.lds_bytes;
+  info->clean_cap = ctx->emit_path.clean_cap;
+  return SG_OK;
 }
 
 int sg_emit_info(sg_ctx* ctx, uint64_t* queued_items, int* requeued) {

@@ -83,6 +83,7 @@ struct sg_ctx {
   bool speculative = false;         // ... and its emit kernels were launched before the text size was known (see run_pass)
   uint64_t slow_items = 0;
   bool slow_overflow = false;
+  sg::EmitPath emit_path = {0, -1, 0, 0};  // the emit kernels of the last pass (sg_emit_path)
   bool results_valid = false;
 
   bool profiling = false;

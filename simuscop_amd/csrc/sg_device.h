@@ -117,6 +117,10 @@ void launch_header(const DevProfile& P, const DevBatch& B, hipStream_t s);
 void launch_emit(const DevProfile& P, const DevBatch& B, hipStream_t s, bool force_generic, hipEvent_t after_main);
 bool emit_uses_fast_kernel(const DevProfile& P, const DevBatch& B);
 int emit_variant(const DevProfile& P);
+// what launch_emit launches for (P, B): the main kernel (SG_EMIT_* of simuscop_amd.h), where emit_slow_kernel's rows live,
+// the main kernel's dynamic LDS and the straight-line kernel's clean-item list
+struct EmitPath { int main_kernel; int slow_rows_lds; uint32_t lds_bytes, clean_cap; };
+EmitPath emit_path(const DevProfile& P, const DevBatch& B, bool force_generic);
 uint32_t record_seg_shift(uint32_t n_slots);
 uint32_t scan_blocks(uint32_t n);
 void launch_scan_u32(const uint32_t* in, uint32_t n, uint64_t* bsum, uint64_t* out, uint64_t* total, hipStream_t s);

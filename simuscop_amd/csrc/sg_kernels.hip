@@ -2412,12 +2412,33 @@ bool emit_uses_fast_kernel(const DevProfile& P, const DevBatch& B) {
   // the straight-line kernel addresses the 2-bit haplotype copies with 32-bit base indexes
   return emit_fast_mode(P) != 0 && B.chains_total < (1ull << 31);
 }
+// (clean_cap: CLEAN_CAP entries per wave, or as many 64s as fit beside a large image: the 41-symbol profiles leave 6.9 KB)
+EmitPath emit_path(const DevProfile& P, const DevBatch& B, bool force_generic) {
+  const EmitLds e = emit_lds(P);
+  EmitPath r;
+  if (!force_generic && emit_uses_fast_kernel(P, B)) {
+    uint32_t clean_cap = (uint32_t)std::min<size_t>(CLEAN_CAP, ((kLdsBytes - e.lds_fast) / (EMIT_WAVES * 2)) & ~(size_t)63);
+    if (getenv("SG_NO_CLEAN_STEPS") != nullptr) clean_cap = 0;
+    if (const char* c = getenv("SG_CLEAN_CAP")) clean_cap = std::min(clean_cap, (uint32_t)strtoul(c, nullptr, 10) & ~63u);  // (tests: a list that overflows)
+    r.main_kernel = SG_EMIT_STRAIGHT_LINE;
+    r.slow_rows_lds = e.sub_lds ? 1 : 0;
+    r.lds_bytes = (uint32_t)(e.lds_fast + (size_t)EMIT_WAVES * clean_cap * 2);
+    r.clean_cap = clean_cap;
+  } else {
+    r.main_kernel = !e.sub_lds ? SG_EMIT_GENERIC_GLOBAL : P.kmer == 3 ? SG_EMIT_GENERIC_K3_LDS : SG_EMIT_GENERIC_LDS;
+    r.slow_rows_lds = -1;
+    r.lds_bytes = (uint32_t)e.lds;
+    r.clean_cap = 0;
+  }
+  return r;
+}
 void launch_emit(const DevProfile& P, const DevBatch& B, hipStream_t s, bool force_generic, hipEvent_t after_main) {
   if (!B.n_slots) {
     if (after_main) (void)hipEventRecord(after_main, s);
     return;
   }
   const EmitLds e = emit_lds(P);
+  const EmitPath path = emit_path(P, B, force_generic);
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -2432,8 +2453,7 @@ void launch_emit(const DevProfile& P, const DevBatch& B, hipStream_t s, bool for
   const uint32_t need = ((B.n_slots + G - 1u) / G + EMIT_WAVES - 1) / EMIT_WAVES;
   if (gx > need) gx = need;
   const dim3 grid(gx, nm);
-  const int mode = (force_generic || !emit_uses_fast_kernel(P, B)) ? 0 : 1;
-  if (mode != 0) {
+  if (path.main_kernel == SG_EMIT_STRAIGHT_LINE) {
     // straight-line kernel: item-stream map, 63 reads per group
     const uint32_t TIf = e.fast_TI;
     const uint32_t fneed = ((B.n_slots + 62u) / 63u + EMIT_WAVES - 1) / EMIT_WAVES;
@@ -2444,11 +2464,8 @@ void launch_emit(const DevProfile& P, const DevBatch& B, hipStream_t s, bool for
     const uint32_t inv_TI = (1u << 20) / TIf + 1u;
     // the list of the one-indel reads' clean items, where the table image leaves room for it (else those reads stay whole
     // in the general steps: same output)
-    // (CLEAN_CAP entries per wave, or as many 64s as fit beside a large image: the 41-symbol profiles leave 6.9 KB)
-    uint32_t clean_cap = (uint32_t)std::min<size_t>(CLEAN_CAP, ((kLdsBytes - e.lds_fast) / (EMIT_WAVES * 2)) & ~(size_t)63);
-    if (getenv("SG_NO_CLEAN_STEPS") != nullptr) clean_cap = 0;
-    if (const char* e = getenv("SG_CLEAN_CAP")) clean_cap = std::min(clean_cap, (uint32_t)strtoul(e, nullptr, 10) & ~63u);  // (tests: a list that overflows)
-    const size_t lds_fast = e.lds_fast + (size_t)EMIT_WAVES * clean_cap * 2;
+    const uint32_t clean_cap = path.clean_cap;
+    const size_t lds_fast = path.lds_bytes;
     auto launch_fast = [&](auto kern) {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast);
       hipLaunchKernelGGL(kern, fgrid, dim3(EMIT_THREADS), lds_fast, s, P, B, TIf, inv_TI, clean_cap);
@@ -2462,7 +2479,7 @@ void launch_emit(const DevProfile& P, const DevBatch& B, hipStream_t s, bool for
     }
     if (after_main) (void)hipEventRecord(after_main, s);
     // the queued items through the generic code (reference-order tables)
-    const size_t slow_sub = e.sub_lds ? (size_t)e.sub_rows * 16 : 0;
+    const size_t slow_sub = path.slow_rows_lds ? (size_t)e.sub_rows * 16 : 0;
     auto launch_slow = [&](auto kern) {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slow_sub);
       hipLaunchKernelGGL(kern, grid, dim3(EMIT_THREADS), slow_sub, s, P, B, e.sub_rows);
@@ -2470,8 +2487,8 @@ void launch_emit(const DevProfile& P, const DevBatch& B, hipStream_t s, bool for
     if (slow_sub) launch_slow(emit_slow_kernel<3, true>);
     else launch_slow(emit_slow_kernel<3, false>);
   } else {
-    if (P.kmer == 3 && e.sub_lds) launch_emit_variant<3, true>(P, B, grid, e.lds, e.sub_rows, TI, RPI, s);
-    else if (e.sub_lds) launch_emit_variant<0, true>(P, B, grid, e.lds, e.sub_rows, TI, RPI, s);
+    if (path.main_kernel == SG_EMIT_GENERIC_K3_LDS) launch_emit_variant<3, true>(P, B, grid, e.lds, e.sub_rows, TI, RPI, s);
+    else if (path.main_kernel == SG_EMIT_GENERIC_LDS) launch_emit_variant<0, true>(P, B, grid, e.lds, e.sub_rows, TI, RPI, s);
     else launch_emit_variant<0, false>(P, B, grid, e.lds, e.sub_rows, TI, RPI, s);
     if (after_main) (void)hipEventRecord(after_main, s);
   }

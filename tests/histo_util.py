@@ -38,7 +38,7 @@ class ProfileTables:
         assert h, path
         info = lambda i: lib.orc_profile_info(h, i)  # noqa: E731
         self.N, self.kmer, self.bins, self.L, self.kc, self.nq = (info(i) for i in range(6))
-        assert self.N == 4 and self.kmer == 3
+        assert self.N == 4 and 1 <= self.kmer <= 6
 
         def arr(which, shape):
             p = lib.orc_profile_array(h, which)
@@ -66,18 +66,29 @@ class ProfileTables:
         self.kmers = []
         for i in range(self.kc):
             lib.orc_profile_kmer(h, i, buf)
-            self.kmers.append(buf.raw[:3].decode())
+            self.kmers.append(buf.raw[:self.kmer].decode())
         lib.orc_profile_free(h)
-        self.bases = "".join(self.kmers[i][2] for i in range(4))   # table order of the bases ("ACTG" in the shipped files)
+        self.bases = "".join(self.kmers[i][-1] for i in range(4))  # table order of the bases ("ACTG" in the shipped files)
         self.code = np.full(256, 255, dtype=np.uint8)
         for i, b in enumerate(self.bases):
             self.code[ord(b)] = i
-        # context index from the codes of the last three source bases (4 = 'X', before the read's start)
-        lut = np.full((5, 5, 5), -1, dtype=np.int32)
+        # context index from the codes of the last K source bases, oldest first in the highest base-5 digit (4 = 'X', before
+        # the read's start: the contexts of a read's first K-1 bases are X-prefixed, Profile.cpp:1660-1663)
+        lut = np.full(5 ** self.kmer, -1, dtype=np.int32)
         sym = self.bases + "X"
         for i, k in enumerate(self.kmers):
-            lut[sym.index(k[0]), sym.index(k[1]), sym.index(k[2])] = i
+            lut[sum(sym.index(ch) * 5 ** (self.kmer - 1 - t) for t, ch in enumerate(k))] = i
         self.ctx_lut = lut
+
+    def context_of(self, sc):
+        """[n, L] base codes (all < 4) -> [n, L] context indexes."""
+        K = self.kmer
+        x = np.full((sc.shape[0], sc.shape[1] + K - 1), 4, dtype=np.int64)
+        x[:, K - 1:] = sc
+        v = np.zeros(sc.shape, dtype=np.int64)
+        for t in range(K):
+            v = v * 5 + x[:, t:t + sc.shape[1]]
+        return self.ctx_lut[v]
 
 
 def read_fasta_one(path):
@@ -170,7 +181,7 @@ def categorical_report(counts, probs, min_expected=5.0):
 def mismatch_cut(T: ProfileTables, mate2):
     """Most mismatches a read without sequencing indels plausibly shows: m + 6 sqrt(m) + 2, m = what the tables expect."""
     p_sub = T.sub[1 if mate2 else 0]
-    ident = np.array([T.bases.index(k[2]) for k in T.kmers])
+    ident = np.array([T.bases.index(k[-1]) for k in T.kmers])
     p_mis = 1.0 - p_sub[np.arange(T.kc), :, ident]                # [kc, bins]
     full = np.array(["X" not in k for k in T.kmers])
     m_exp = float(p_mis[full].mean(axis=0)[(np.arange(T.L) * T.bins // T.L)].sum())
@@ -220,9 +231,7 @@ def sub_and_quality_counts(T: ProfileTables, fq: Fastq, src_of, rows, mate2):
         sc, called, q = sc[ok].astype(np.int32), called[ok].astype(np.int32), q[ok].astype(np.int32) - 33
         used += int(ok.sum())
         mism += int(d[ok].sum())
-        x = np.full((sc.shape[0], L + 2), 4, dtype=np.int32)
-        x[:, 2:] = sc
-        ctx = T.ctx_lut[x[:, :-2], x[:, 1:-1], x[:, 2:]]
+        ctx = T.context_of(sc)
         assert (ctx >= 0).all()
         b = np.broadcast_to(jbin, ctx.shape)
         sub += np.bincount(((b * T.kc + ctx) * 4 + called).ravel(), minlength=sub.size).reshape(sub.shape)
@@ -240,11 +249,12 @@ def check_sub_and_quality(T: ProfileTables, sub, qual, mate2, what):
     off = sub.copy().astype(np.float64)
     ident = np.zeros_like(p_sub, dtype=bool)
     for i, k in enumerate(T.kmers):
-        ident[:, i, T.bases.index(k[2])] = True
+        ident[:, i, T.bases.index(k[-1])] = True
     n = sub.sum(axis=-1, keepdims=True)
     e = n * p_sub
     sel = (~ident) & (e >= 5)
-    chi2 = (((off - e) ** 2)[sel] / e[sel]).sum()
+    # (binomial variance n p (1 - p) per cell: the shipped rows' p ~ 1e-3 make it n p, the generated shapes' are up to 0.3)
+    chi2 = (((off - e) ** 2)[sel] / (e * np.maximum(1.0 - p_sub, 1e-12))[sel]).sum()
     d2 = int(sel.sum())
     z2 = (chi2 - d2) / np.sqrt(2.0 * d2)
     assert abs(z2) < Z_MAX, f"{what} G1 substituted outcomes: chi2 z={z2:.2f} dof={d2}"
@@ -375,7 +385,8 @@ def check_read_lengths(T: ProfileTables, lens, what):
     z, dof, pmin, cells, worst = categorical_report(counts[None, :], pmf[None, :])
     exp_mean = float((np.arange(len(pmf)) * pmf).sum())
     sd = float(np.sqrt(((np.arange(len(pmf)) - exp_mean) ** 2 * pmf).sum()))
-    zm = (lens.mean() - exp_mean) / (sd / np.sqrt(len(lens)))
+    # (a profile without sequencing indels: one possible length, which every read must have)
+    zm = (lens.mean() - exp_mean) / (sd / np.sqrt(len(lens))) if sd > 0 else (0.0 if lens.mean() == exp_mean else np.inf)
     rep = {"g3_z": round(z, 2), "g3_dof": dof, "g3_pmin": pmin, "g3_mean_z": round(float(zm), 2), "mean_length": round(float(lens.mean()), 5),
            "expected_mean_length": round(exp_mean, 5), "changed_fraction": round(float((lens != T.L).mean()), 4),
            "expected_changed_fraction": round(float(1 - pmf[T.L]), 4)}
@@ -433,22 +444,24 @@ def normal_report(z):
 
 # ---- a whole run --------------------------------------------------------------------------------------------------------
 def histogram_config(cases, wd, profile, layout, coverage, insert, length=1400000, seed=83):
-    """One contig without N runs (a single segment: 1.4 Mbp < 1.5 segMaxSize, Genome.cpp:741-763), ploidy 1, no variants."""
+    """One contig without N runs (a single segment: 1.4 Mbp < 1.5 segMaxSize, Genome.cpp:741-763), ploidy 1, no variants.
+    `profile`: a shipped profile's key in cases.PROFILES, or the path of another profile file."""
     import os
     from simuscop_amd import synth
     fa = os.path.join(wd, "ref.fa")
     synth.write_fasta(fa, [("chr1", length)], seed=seed, n_runs=False)
     cfg = os.path.join(wd, "config.txt")
-    cases._config(cfg, ref=fa, profile=os.path.join(cases.TESTDATA, cases.PROFILES[profile]), name="h", output=os.path.join(wd, "out"),
+    cases._config(cfg, ref=fa, profile=profile if os.path.isfile(profile) else os.path.join(cases.TESTDATA, cases.PROFILES[profile]), name="h", output=os.path.join(wd, "out"),
                   layout=layout, threads=1, verbose=0, coverage=coverage, insertSize=insert, ploidy=1)
     return cfg, fa
 
 
-def analyse_run(lib, cases, profile, layout, insert, fasta, files, what, want_gc=True):
-    """All closed-form families on the FASTQ files of one run (see the module docstring).  Returns the report."""
+def analyse_run(lib, cases, profile, layout, insert, fasta, files, what, want_gc=True, profile_path=None):
+    """All closed-form families on the FASTQ files of one run (see the module docstring).  Returns the report.
+    `profile_path`: a profile file other than the shipped one `profile` names."""
     import os
     paired = layout == "PE"
-    T = ProfileTables(lib, os.path.join(cases.TESTDATA, cases.PROFILES[profile]), paired, insert)
+    T = ProfileTables(lib, profile_path or os.path.join(cases.TESTDATA, cases.PROFILES[profile]), paired, insert)
     ref = read_fasta_one(fasta)
     L = T.L
     rep = {"profile": profile, "layout": layout, "read_length": L}

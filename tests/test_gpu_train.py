@@ -312,6 +312,16 @@ def test_seqtoprofile_writes_the_profile_of_the_restatement(exome, oracle_lib, t
         r = subprocess.run([exe, "--sam", sam_path, "-v", vcf, "-r", fa, "-o", got5, "-k", "5", "-B", "20", "--quiet"], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         assert open(want5, "rb").read().split(b"\n", 1)[1] == open(got5, "rb").read().split(b"\n", 1)[1]
+        # ... and the sampler on what the trainer wrote at other shapes: -k 5 -B 20, -k 1 -B 10 and -B = the read length.
+        # Trained tables are sparse: all-zero substitution rows (unseen contexts copy the base) and all-zero quality rows
+        # (the last symbol) as real data gives them.  simuReads on each = oracle(philox) on it, byte for byte.
+        got1, gotL = os.path.join(wd, "got1.profile"), os.path.join(wd, "gotL.profile")
+        for path, opts in ((got1, ["-k", "1", "-B", "10"]), (gotL, ["-B", str(T.L)])):
+            r = subprocess.run([exe, "--sam", sam_path, "-v", vcf, "-r", fa, "-o", path, "--quiet"] + opts, capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+        assert "binCount: %d" % T.L in open(gotL).read(4000)
+        for path in (got5, got1, gotL):
+            _sample_like_the_oracle(oracle_lib, path, fa1, os.path.join(wd, os.path.basename(path) + ".sim"))
     REF, SHIM = os.path.join(ROOT, "oracle", "_ref", "simuReads"), os.path.join(ROOT, "oracle", "_ref", "libfakeclock.so")
     if os.path.exists(REF) and not exome:
         cfg, out = os.path.join(wd, "sim.txt"), os.path.join(wd, "sim_out")
@@ -325,6 +335,16 @@ def test_seqtoprofile_writes_the_profile_of_the_restatement(exome, oracle_lib, t
             os.remove(os.path.join(out, f))
         assert oracle_lib.orc_simulate(cfg.encode(), 0, cases.FAKE_SEC, cases.FAKE_NSEC, b"", 1) == 0
         assert md5(out) == ref_md5 and ref_md5
+
+
+def _sample_like_the_oracle(oracle_lib, profile, fa, wd):
+    """simuReads on `profile` (PE, 2x) = oracle(philox) on it, byte for byte; the first differing read is reported."""
+    import test_gpu_profile_shapes as GS
+    cfg = os.path.join(wd, "sim.txt")
+    os.makedirs(wd, exist_ok=True)
+    cases._config(cfg, ref=fa, profile=profile, name="t", output=os.path.join(wd, "unused"), layout="PE", threads=1, verbose=0, coverage=2,
+                  insertSize=350, ploidy=2)
+    GS.assert_gpu_equals_oracle(oracle_lib, cfg, wd, os.path.basename(profile))
 
 
 def _random_training_case(rng, wd):

@@ -30,11 +30,17 @@ def _counts(lib, cdf):
 
 @pytest.mark.parametrize("prof", PROFILES)
 def test_tables_keep_every_count(prof, oracle_lib):
+    check_tables_keep_every_count(oracle_lib, os.path.join(ROOT, "tests", "golden", "testData", prof), prof)
+
+
+def check_tables_keep_every_count(oracle_lib, path, prof):
+    """Every substitution row (a sample of contexts x every bin, both mates) and every quality row of the profile file `path`:
+    the product's rows = the oracle's, and they give every outcome exactly its count of draws."""
     lib = simuscop_amd.load_engine()
     oracle_lib.orc_profile_sub_row.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]
     oracle_lib.orc_profile_alias_row.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8),
                                                  C.POINTER(C.c_uint8)]
-    h = oracle_lib.orc_profile_load(os.path.join(ROOT, "tests", "golden", "testData", prof).encode(), 1, 350)
+    h = oracle_lib.orc_profile_load(path.encode(), 1, 350)
     assert h
     try:
         bins, kc, nq = (oracle_lib.orc_profile_info(h, i) for i in (2, 4, 5))
@@ -43,11 +49,15 @@ def test_tables_keep_every_count(prof, oracle_lib):
         rng = np.random.default_rng(11)
         # ---- substitution rows (both mates): a sample of contexts x every bin ----
         kbuf = C.create_string_buffer(8)
+        bases = ""
+        for ki in range(4):   # the one-base contexts, in the profile's base order
+            oracle_lib.orc_profile_kmer(h, ki, kbuf)
+            bases += kbuf.value.decode()[-1]
         for which, mate2 in ((2, 0), (3, 1)):
             sub = np.ctypeslib.as_array(oracle_lib.orc_profile_array(h, which), shape=(kc, bins, 4))
-            for ki in sorted(set(rng.integers(0, kc, 24).tolist() + [0, 3, 4, 19, 20, kc - 1])):
+            for ki in sorted(k for k in set(rng.integers(0, kc, 24).tolist() + [0, 3, 4, 19, 20, kc - 1]) if k < kc):
                 oracle_lib.orc_profile_kmer(h, ki, kbuf)
-                cd = "ACTG".index(kbuf.value.decode()[-1])
+                cd = bases.index(kbuf.value.decode()[-1])
                 for b in range(bins):
                     row = np.ascontiguousarray(sub[ki, b])
                     n = _counts(lib, row)
