@@ -471,6 +471,8 @@ int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap,
   while (p < bytes && n < cap) {
     if (bytes - p < 12) break;
     if (b[p] != 31 || b[p + 1] != 139 || b[p + 2] != 8 || !(b[p + 3] & 4)) return bad("not a gzip member with an extra field");
+    // BGZF fixes FLG = 4 (SAMv1 section 4.1); FNAME, FCOMMENT or FHCRC would also move the DEFLATE data from 12 + XLEN
+    if (b[p + 3] != 4) return bad("gzip flags other than FEXTRA");
     const uint32_t xlen = b[p + 10] | ((uint32_t)b[p + 11] << 8);
     if (p + 12 + xlen > bytes) break;
     int64_t bsize = -1;

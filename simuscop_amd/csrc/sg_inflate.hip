@@ -12,6 +12,8 @@
 //                   bytes), the check against the trailer, and one copy out.
 // A member that is not a well-formed DEFLATE stream gets a verdict (sg_bam.h) and writes nothing; every read stays inside
 // the batch and every write inside the member's own 64 KiB of LDS / its ISIZE bytes of output.
+// Bytes left over between the final block and the trailer are accepted, as zlib's inflate() accepts them (it returns
+// Z_STREAM_END with input left): the member is taken when its output has the trailer's ISIZE and CRC-32.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -1,6 +1,6 @@
 """BAM files for the tests (SAMv1 sections 4.1-4.2), with no samtools / pysam: a writer from SAM fields with BGZF members of
-any size and zlib level / strategy, the lines `samtools view -F 0xD04 -q 20` prints of such a file (the eleven mandatory
-fields), and the `bin` of a record (reg2bin, SAMv1 section 5.3)."""
+any size and zlib level / strategy, optional fields of every type (SAMv1 section 4.2.4), the lines `samtools view -F 0xD04
+-q 20` prints of such a file (the eleven mandatory fields only), and the `bin` of a record (reg2bin, SAMv1 section 5.3)."""
 import struct
 import zlib
 
@@ -89,10 +89,49 @@ def header(refs, text=b""):
     return b"".join(out)
 
 
-def record(fields, ref_id, use_cg=False, aux=b"", name=None):
+AUX_FORMAT = {"A": "c", "c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f", "d": "d"}
+AUX_ARRAYS = "cCsSiIf"
+
+
+def aux_tag(tag, ty, value):
+    """One optional field: tag (two bytes), a type letter of A c C s S i I f d Z H, or "B" + the element type for an array."""
+    if ty in ("Z", "H"):
+        return tag + ty.encode() + value + b"\0"
+    if ty[0] == "B":
+        return tag + b"B" + ty[1].encode() + struct.pack("<I", len(value)) + b"".join(struct.pack("<" + AUX_FORMAT[ty[1]], v) for v in value)
+    return tag + ty.encode() + struct.pack("<" + AUX_FORMAT[ty], value)
+
+
+def aux_every_type(rng):
+    """One field of each of the eleven scalar and string types and one array of each of the seven element types: the twelve
+    types other than a CG array that a reader steps over, as a list of fields.  Values hold bytes that read as type letters."""
+    lo = {"c": -128, "C": 0, "s": -32768, "S": 0, "i": -2 ** 31, "I": 0}
+    hi = {"c": 127, "C": 255, "s": 32767, "S": 65535, "i": 2 ** 31 - 1, "I": 2 ** 32 - 1}
+    out = [aux_tag(b"XA", "A", bytes([rng.choice(b"ZBHid")]))]
+    for k, ty in enumerate("cCsSiI"):
+        out.append(aux_tag(b"X%d" % k, ty, rng.choice((lo[ty], hi[ty], rng.randrange(lo[ty], hi[ty] + 1)))))
+    out += [aux_tag(b"XF", "f", rng.random() * 100), aux_tag(b"XD", "d", rng.random() * 1e300),
+            aux_tag(b"XZ", "Z", bytes(rng.choice(b"CGBIZH ") for _ in range(rng.randrange(0, 40)))),
+            aux_tag(b"XH", "H", b"%02X" % rng.randrange(256) * rng.randrange(0, 9))]
+    for k, sub in enumerate(AUX_ARRAYS):
+        vals = [rng.random() for _ in range(rng.randrange(0, 9))] if sub == "f" else [rng.randrange(lo[sub], hi[sub] + 1) for _ in range(rng.randrange(0, 9))]
+        out.append(aux_tag(b"Y%d" % k, "B" + sub, vals))
+    return out
+
+
+def aligner_tags(rng, L):
+    """NM:i MD:Z AS:i XS:i RG:Z with seeded values, in the integer widths an aligner's writer picks (the smallest that holds)"""
+    def small(tag, v):
+        return aux_tag(tag, "C" if v < 256 else "S" if v < 65536 else "I", v)
+    md = b"%d%s%d" % (rng.randrange(L), bytes([rng.choice(b"ACGT")]), rng.randrange(L)) if rng.random() < 0.5 else b"%d" % L
+    return b"".join([small(b"NM", rng.choice((0, 0, 1, 2, 300))), aux_tag(b"MD", "Z", md), small(b"AS", rng.randrange(70000)),
+                     small(b"XS", rng.randrange(300)), aux_tag(b"RG", "Z", b"lane%d" % rng.randrange(4))])
+
+
+def record(fields, ref_id, use_cg=False, aux=b"", name=None, aux_behind_cg=b"", cg_type=b"I"):
     """One record from the eleven SAM fields (bytes).  A CIGAR that does not parse is stored as none; a quality string of
     another length than the sequence is stored as absent (0xFF); use_cg / more than 65,535 operations: the placeholder
-    kSmN and the real CIGAR in CG:B:I."""
+    kSmN and the real CIGAR in CG:B:I (CG:B:i with cg_type b"i"), between the optional fields `aux` and `aux_behind_cg`."""
     qname, flag, rname, pos, mapq, cigar, rnext, pnext, tlen, seq, qual = fields[:11]
     rid = -1 if rname == b"*" else ref_id[rname]
     nrid = rid if rnext == b"=" else -1 if rnext == b"*" else ref_id[rnext]
@@ -101,8 +140,9 @@ def record(fields, ref_id, use_cg=False, aux=b"", name=None):
     ref_len = sum(n for n, o in ops if o in (0, 2, 3, 7, 8))
     pos0 = int(pos) - 1
     if use_cg or len(ops) > 65535:
-        aux = aux + b"CGBI" + struct.pack("<I", len(ops)) + b"".join(struct.pack("<I", n << 4 | o) for n, o in ops)
+        aux = aux + b"CGB" + cg_type + struct.pack("<I", len(ops)) + b"".join(struct.pack("<I", n << 4 | o) for n, o in ops)
         ops = [(l_seq, 4), (ref_len, 3)]
+    aux += aux_behind_cg
     bin_ = reg2bin(pos0, pos0 + max(ref_len, 1)) if pos0 >= 0 else 4680
     seq_b = bytearray((l_seq + 1) // 2)
     for i in range(l_seq):
@@ -117,9 +157,11 @@ def record(fields, ref_id, use_cg=False, aux=b"", name=None):
     return struct.pack("<I", len(body)) + body
 
 
-def bam_stream(lines, refs=None, text=b"@HD\tVN:1.6\n", use_cg=()):
+def bam_stream(lines, refs=None, text=b"@HD\tVN:1.6\n", use_cg=(), aux=None):
     """Decompressed BAM (header + records) of SAM lines (bytes, tab separated).  `refs`: (name, length) in order; names the
-    lines use that it lacks are appended.  use_cg: indices of lines stored with the CG:B:I placeholder."""
+    lines use that it lacks are appended.  use_cg: indices of lines stored with the CG:B:I placeholder.  aux: {line index:
+    the record's optional fields as bytes, or (fields before CG, fields behind CG, b"I" or b"i")}."""
+    aux = aux or {}
     refs = list(refs or [])
     ref_id = {n: i for i, (n, _) in enumerate(refs)}
     recs = []
@@ -129,7 +171,9 @@ def bam_stream(lines, refs=None, text=b"@HD\tVN:1.6\n", use_cg=()):
             if n not in (b"*", b"=") and n not in ref_id:
                 ref_id[n] = len(refs)
                 refs.append((n, 1 << 30))
-        recs.append(record(f, ref_id, use_cg=i in use_cg))
+        a = aux.get(i, b"")
+        a = (a, b"", b"I") if isinstance(a, bytes) else a
+        recs.append(record(f, ref_id, use_cg=i in use_cg, aux=a[0], aux_behind_cg=a[1], cg_type=a[2]))
     return header(refs, text) + b"".join(recs)
 
 
@@ -166,11 +210,17 @@ def _cigar_ops(r):
             tag, ty = r[p:p + 2], chr(r[p + 2])
             p += 3
             if ty in "ZH":
-                p = r.index(b"\0", p) + 1
+                p = r.find(b"\0", p) + 1
+                if p == 0:   # not terminated before the record ends: nothing lies behind it
+                    break
             elif ty == "B":
+                if p + 5 > end:
+                    break
                 sub, n = chr(r[p]), struct.unpack_from("<I", r, p + 1)[0]
+                if sub not in sizes:
+                    break
                 if tag == b"CG" and sub in "Ii":
-                    if len(ops) <= n < 1 << 29:
+                    if len(ops) <= n < 1 << 29 and p + 5 + 4 * n <= end:
                         ops = [struct.unpack_from("<I", r, p + 5 + 4 * i)[0] for i in range(n)]
                     break
                 p += 5 + n * sizes[sub]

@@ -46,6 +46,36 @@ def test_record_layout_round_trips_through_the_renderer():
     assert B.reg2bin(0, 1) == 4681 and B.reg2bin(0, 1 << 14) == 4681 and B.reg2bin(0, (1 << 14) + 1) == 585 and B.reg2bin(0, 1 << 29) == 0
 
 
+def test_optional_fields_of_every_type_leave_the_eleven_fields_alone():
+    rng = random.Random(9)
+    lines = [b"r%d\t0\tchr1\t%d\t60\t3M%dI4M\t=\t0\t0\tACGTACG%s\tIIIIIII%s" % (i, 50 + i, i + 1, b"A" * (i + 1), b"F" * (i + 1)) for i in range(6)]
+    plain = B.bam_stream(lines, refs=[(b"chr1", 1000)], use_cg=set(range(6)))
+    every = B.aux_every_type(rng)
+    assert len(every) == 18 and sorted(t[2:3] for t in every) == sorted([bytes([c]) for c in b"AcCsSiIfdZH"] + [b"B"] * 7)
+    assert sorted(t[3:4] for t in every if t[2:3] == b"B") == sorted(bytes([c]) for c in B.AUX_ARRAYS.encode())
+    al = B.aligner_tags(rng, 7)
+    assert [al.count(t) for t in (b"NM", b"MD", b"AS", b"XS", b"RG")] == [1] * 5
+    aux = {0: (b"", b"".join(every) + al, b"I"), 1: (b"".join(every) + al, b"", b"I"), 2: (b"".join(every[:9]), b"".join(every[9:]), b"I"),
+           3: (b"".join(every[::-1]), al, b"i"), 4: al, 5: (b"".join(every[11:]), b"".join(every[:11]), b"i")}
+    d = B.bam_stream(lines, refs=[(b"chr1", 1000)], use_cg=set(range(6)), aux=aux)
+    assert len(d) > len(plain) + 1000
+    assert B.view(d) == B.view(plain) == b"".join(ln + b"\n" for ln in lines)   # CG:B:I and CG:B:i found behind, between and before them
+    names, recs = B.parse_stream(d)
+    for (_, r), ln in zip(recs, lines):
+        cigar = ln.split(b"\t")[5]
+        assert [(o >> 4, o & 15) for o in B._cigar_ops(r)] == B.parse_cigar(cigar)
+        assert r.count(b"CGB") >= 1 and int.from_bytes(r[16:18], "little") == 2
+    # an unknown type letter hides the CG behind it; a Z field that is not terminated runs to the record's end; a CG array
+    # shorter than n_cigar is ignored (htslib's bam_tag2cigar)
+    d = B.bam_stream(lines[:1], refs=[(b"chr1", 1000)], use_cg={0}, aux={0: (b"XQ?abcd", b"", b"I")})
+    assert B.view(d).split(b"\t")[5] == b"8S7N"   # (l_seq 8, 7 reference bases: the placeholder itself)
+    d = B.bam_stream([b"r\t0\tchr1\t5\t60\t7S9N\t=\t0\t0\tACGTACG\tIIIIIII"], refs=[(b"chr1", 1000)], aux={0: al + b"XZZnever ends"})
+    assert B.view(d).split(b"\t")[5] == b"7S9N" and d.endswith(b"never ends")
+    short = B.aux_tag(b"CG", "BI", [7 << 4])
+    d = B.bam_stream([b"r\t0\tchr1\t5\t60\t7S9N\t=\t0\t0\tACGTACG\tIIIIIII"], refs=[(b"chr1", 1000)], aux={0: short})
+    assert B.view(d).split(b"\t")[5] == b"7S9N"
+
+
 def _members_c(buf, cap=1 << 20):
     lib = simuscop_amd.load_engine()
     off = (C.c_uint64 * cap)()
