@@ -284,6 +284,12 @@ void sg_windows_drop(sg_ctx* ctx);  /* frees every window-weight store of the co
  * (lib/seqwriter/SeqWriter.cpp:41-54) has no such mode: additive.                                   */
 int sg_compress(sg_ctx* ctx, uint64_t* gz_bytes_r1, uint64_t* gz_bytes_r2);
 int sg_fetch_compressed(sg_ctx* ctx, int mate, uint64_t offset, uint64_t bytes, void* host_dst);
+/* The same compressor on text in host memory, for tests and for callers that hold text of their own: `bytes` bytes of
+ * `text` -> ceil(bytes / 32768) BGZF members in `out`, in order, without the EOF member of sg_bgzf_eof; *out_bytes = how
+ * many bytes they take (SG_ERR_OVERFLOW when out_cap is too small: call again).  bytes = 0 gives *out_bytes = 0.  Any byte
+ * value is legal in the text, 0x00 and 0xFF included; no sampling pass is needed and none is disturbed.  The text is copied
+ * before the call returns.  The same text gives the same members, call after call.                   */
+int sg_deflate_bgzf(sg_ctx* ctx, const void* text, uint64_t bytes, void* out, uint64_t out_cap, uint64_t* out_bytes);
 /* ---- detached outputs: drain one batch while the next is sampled ------------------------------------- */
 /* After sg_result (and sg_compress, if wanted) the FASTQ text -- and its BGZF form -- can be taken out of
  * the context: the handle owns the device buffers and a copy stream of its own, so sg_outputs_fetch may

@@ -22,7 +22,7 @@ SG_K_NAMES = ["plan", "namebase", "indel", "scan", "emit", "emit_slow"]
 ENGINE_SYMBOLS = [
     "sg_create", "sg_destroy", "sg_last_error", "sg_set_stream", "sg_set_seed", "sg_set_strict_bases", "sg_load_profile",
     "sg_upload_haplotypes", "sg_reference_begin", "sg_reference_chunk", "sg_sync", "sg_reference_scan",
-    "sg_reference_commit", "sg_build_haplotypes", "sg_haplotype_codes", "sg_compress", "sg_fetch_compressed",
+    "sg_reference_commit", "sg_build_haplotypes", "sg_haplotype_codes", "sg_compress", "sg_fetch_compressed", "sg_deflate_bgzf",
     "sg_bgzf_eof", "sg_deflate_plan", "sg_detach_outputs", "sg_outputs_sizes", "sg_outputs_fetch",
     "sg_outputs_last_error", "sg_release_outputs", "sg_plan", "sg_sample", "sg_result", "sg_fetch", "sg_device_output",
     "sg_gc_percent", "sg_set_profiling", "sg_kernel_times", "sg_emit_info", "sg_emit_variant", "sg_emit_path", "sg_cdf_count_le", "sg_fetch_range", "sg_host_alloc",
@@ -174,6 +174,7 @@ def load_engine():
     lib.sg_haplotype_codes.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p]
     lib.sg_compress.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.sg_fetch_compressed.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
+    lib.sg_deflate_bgzf.argtypes = [vp, C.c_char_p, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.sg_bgzf_eof.argtypes = [C.c_char_p]
     lib.sg_deflate_plan.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]

@@ -50,7 +50,8 @@ struct sg_ctx {
   sg::DevBatch B{};
   DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_actual, win_namebase, events, recoff, meta, totals, bsum,
       out1, out2, gcw, gco, gcm, slowq, ref_raw, ref_codes, ref_meta, hap_work, gz1, gz2, gz_work,
-      infl_src, infl_meta, infl_out, infl_crc;   // sg_inflate_bgzf (infl_crc also serves the training session's BAM input)
+      infl_src, infl_meta, infl_out, infl_crc,   // sg_inflate_bgzf (infl_crc also serves the training session's BAM input)
+      defl_src, defl_out;                        // sg_deflate_bgzf: the caller's text and its members
   // the haplotype chains in `chains` (sg_upload_haplotypes, sg_build_haplotypes): chain c holds len[c] bases from off[c] on;
   // chain_meta holds the same on the device for the kernels, the host checks against this copy
   struct ChainLayout {
