@@ -314,6 +314,70 @@ int sg_bgzf_eof(uint8_t out[28]);
 uint32_t sg_deflate_plan(const uint64_t lit_counts[286], const uint64_t dist_counts[30], uint8_t lit_lens[286], uint32_t lit_codes[286],
                          uint8_t dist_lens[30], uint32_t dist_codes[30], uint32_t len_tokens[260], uint32_t* prefix_words, uint32_t cap);
 
+/* ---- truth alignments: where every read of a pass came from, as BAM records (simuReads --truth-bam) ------------------
+ * The reference has no such output (Segment::yieldReads keeps pos % segsize in the read's name and nothing else,
+ * Segment.cpp:780); its trainer reads alignments (Profile::processRead, lib/profile/Profile.cpp:228-510), and these
+ * records are alignments it can read.  Additive: a context that never calls sg_truth_map launches no kernel of this
+ * part and holds no device memory for it.
+ *
+ * The rule (sg_truth_align; host only, no context): a read's template is tmpl_len bases of its chain from tmpl_off on, in
+ * chain direction -- the fragment's first L bases for a forward read, its last L for a reverse read.  Walked over the
+ * chain's pieces: a reference piece (kind 0) gives M, a literal piece (kind 1) I; a forward gap between consecutive
+ * reference pieces of one contig gives D, or N when a segment's haplotype string began in between (seg_first); any other
+ * joint (the position goes back, the contig changes) ends the alignment and the rest of the template is S.  The
+ * sequencing events (ev_pack form: j | len << 16 | deletion << 31, ascending and apart, j + len <= tmpl_len for a
+ * deletion) are in read direction: index j counts from the template's chain end for a reverse read.  An insertion puts
+ * its bases behind template base j (I; S inside a clipped part), a deletion takes bases [j, j + len) away: D for a base
+ * that was M, nothing for a literal or clipped base.  Then: equal neighbours merge; what lies in front of the first and
+ * behind the last M loses its D / N and becomes one S; *pos0 is the 0-based position of the first M base.  The
+ * operations (len << 4 | op, op 0 M 1 I 2 D 3 N 4 S) are in reference direction.  A read without an M base is unmapped:
+ * *n_ops = 0, *contig = -1.  SG_ERR_OVERFLOW when `cap` is too small (*n_ops says how many there are).
+ *   sg_truth_map     after sg_build_haplotypes, with the pieces of that call (the engine keeps no copy of them for a
+ *                    caller that never asks): seg_first[i] = 1 when piece i is the first piece of a segment's haplotype
+ *                    string; ref_ids[c] = BAM refID of contig c (NULL: c).  Sorts the copy list by (chain, dst) and
+ *                    puts it on the device.  The pieces of a chain must tile it, none of length 0; a refused call
+ *                    leaves an earlier map as it was.  The chains of sg_upload_haplotypes have no copy list:
+ *                    SG_ERR_INVALID, as from every call below without a map
+ *   sg_truth_pieces  the sorted pieces of one chain, as sg_truth_align takes them (contig: the one of sg_hap_piece)
+ *   sg_truth_reads   after sg_result: where reads [first_slot, first_slot + n) of mate 0 / 1 came from
+ *   sg_truth_bam     after sg_result, before sg_detach_outputs: the BAM records (SAMv1 section 4.2, no optional fields) of
+ *                    the pass's reads in FASTQ order -- slot by slot, mate 1 then mate 2; unused slots give nothing --
+ *                    and their BGZF members (the compressor of sg_compress; no header, no EOF block).  QNAME is the FASTQ
+ *                    name without '@' and "/1", SEQ / QUAL the FASTQ's, turned round for a reverse read; FLAG 0 / 16 (SE),
+ *                    99 / 147 (PE), MAPQ 60; RNEXT / PNEXT the mate's place, TLEN the span of the pair's M bases (positive
+ *                    for the leftmost mate).  An unmapped read: flag 0x4 without 0x10, MAPQ 0, no CIGAR, at its mate's
+ *                    place (-1 / -1 without one); its mate gets 0x8 and loses 0x2, TLEN 0 for both.
+ *   sg_fetch_truth   bytes [offset, offset + bytes) of the record stream (compressed = 0) or of its BGZF members (1)
+ *   sg_truth_info    records and unmapped records of the last sg_truth_bam                                          */
+typedef struct sg_truth_piece {
+  uint64_t dst;        /* offset in the chain                                                    */
+  uint64_t src;        /* kind 0: 0-based position on contig `contig`                            */
+  uint32_t len;
+  uint32_t contig;
+  uint32_t kind;       /* 0 reference, 1 literal                                                 */
+  uint32_t seg_first;  /* 1: first piece of a segment's haplotype string                         */
+} sg_truth_piece;
+int sg_truth_align(const sg_truth_piece* pieces, uint64_t n_pieces, uint64_t tmpl_off, uint32_t tmpl_len, int reverse,
+                   const uint32_t* events, uint32_t n_events, int32_t* contig, int64_t* pos0, uint32_t* cigar, uint32_t cap,
+                   uint32_t* n_ops);
+typedef struct sg_truth_read {
+  uint32_t live;       /* 0: unused slot                                                         */
+  uint32_t chain;
+  uint32_t reverse;
+  uint32_t read_len;   /* bases of the read (template length + inserted - deleted)               */
+  uint64_t tmpl_off;   /* chain-local offset of the template's first base                        */
+  uint32_t n_events;   /* from the read's row, not from the events buffer                        */
+  uint32_t inside;     /* 0: the template does not lie inside its chain (the record is unmapped) */
+  uint32_t events[SG_MAX_EVENTS];
+} sg_truth_read;
+int sg_truth_map(sg_ctx* ctx, const sg_hap_piece* pieces, const uint8_t* seg_first, uint64_t n_pieces, const int32_t* ref_ids,
+                 uint32_t n_ref_ids);
+int sg_truth_pieces(sg_ctx* ctx, uint32_t chain, sg_truth_piece* out, uint64_t cap, uint64_t* n);
+int sg_truth_reads(sg_ctx* ctx, int mate, uint32_t first_slot, uint32_t n, sg_truth_read* out);
+int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes);
+int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes, void* host_dst);
+int sg_truth_info(sg_ctx* ctx, uint64_t* records, uint64_t* unmapped);
+
 /* When enabled, HIP events bracket every kernel of sg_sample on the ctx's stream;
  * sg_kernel_times() then returns the last pass's per-kernel milliseconds (after sg_result).     */
 int sg_set_profiling(sg_ctx* ctx, int enable);

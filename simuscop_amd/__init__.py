@@ -31,6 +31,7 @@ ENGINE_SYMBOLS = [
     "sg_train_begin", "sg_train_feed", "sg_train_capped", "sg_train_finish", "sg_train_end",
     "sg_bgzf_members", "sg_inflate_bgzf", "sg_train_bam_start", "sg_train_feed_bgzf", "sg_train_bam_info",
     "sg_release_cached_memory",
+    "sg_truth_align", "sg_truth_map", "sg_truth_pieces", "sg_truth_reads", "sg_truth_bam", "sg_fetch_truth", "sg_truth_info",
 ]
 
 
@@ -92,6 +93,18 @@ class SgHapPiece(C.Structure):
                 ("contig", C.c_uint32), ("kind", C.c_uint32)]
 
 
+class SgTruthPiece(C.Structure):
+    """sg_truth_piece: one piece of a chain's copy list, as sg_truth_align takes it"""
+    _fields_ = [("dst", C.c_uint64), ("src", C.c_uint64), ("len", C.c_uint32), ("contig", C.c_uint32), ("kind", C.c_uint32),
+                ("seg_first", C.c_uint32)]
+
+
+class SgTruthRead(C.Structure):
+    """sg_truth_read: where one read of a pass came from (sg_truth_reads)"""
+    _fields_ = [("live", C.c_uint32), ("chain", C.c_uint32), ("reverse", C.c_uint32), ("read_len", C.c_uint32),
+                ("tmpl_off", C.c_uint64), ("n_events", C.c_uint32), ("inside", C.c_uint32), ("events", C.c_uint32 * 32)]
+
+
 class SgHapPatch(C.Structure):
     _fields_ = [("dst", C.c_uint64), ("chain", C.c_uint32), ("base", C.c_uint32)]
 
@@ -101,7 +114,7 @@ class SimuOptions(C.Structure):
                 ("fetch", C.c_int32), ("quiet", C.c_int32), ("shard_rank", C.c_int32), ("shard_world", C.c_int32),
                 ("output_dir", C.c_char_p), ("repeat_sample", C.c_int32), ("host_haplotypes", C.c_int32), ("gzip", C.c_int32),
                 ("shard_contigs", C.c_int32), ("no_eof_block", C.c_int32), ("exchange", C.c_void_p), ("exchange_user", C.c_void_p),
-                ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32)]
+                ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32)]
 
 
 # simu_options.exchange: all-reduce(sum) of n doubles over the ranks, in place
@@ -122,7 +135,9 @@ class SimuStats(C.Structure):
                 ("queued_items", C.c_uint64), ("requeued_batches", C.c_uint64), ("t_engine", C.c_double),
                 ("t_reference", C.c_double), ("t_hap_device", C.c_double), ("t_plan_api", C.c_double), ("t_compress", C.c_double), ("gz_bytes", C.c_uint64),
                 ("emit_kernel", C.c_int32), ("emit_slow_rows_lds", C.c_int32), ("emit_lds_bytes", C.c_uint32),
-                ("emit_clean_cap", C.c_uint32)]
+                ("emit_clean_cap", C.c_uint32),
+                ("truth_records", C.c_uint64), ("truth_unmapped", C.c_uint64), ("truth_bytes", C.c_uint64),
+                ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double)]
 
 
 _engine = None
@@ -206,6 +221,14 @@ def load_engine():
     lib.sg_row_symbols.restype = C.c_uint32
     lib.sg_alias_row.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8),
                                  C.POINTER(C.c_uint8)]
+    lib.sg_truth_align.argtypes = [C.POINTER(SgTruthPiece), C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint32,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.sg_truth_map.argtypes = [vp, C.POINTER(SgHapPiece), C.c_char_p, C.c_uint64, C.POINTER(C.c_int32), C.c_uint32]
+    lib.sg_truth_pieces.argtypes = [vp, C.c_uint32, C.POINTER(SgTruthPiece), C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.sg_truth_reads.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(SgTruthRead)]
+    lib.sg_truth_bam.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.sg_fetch_truth.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
+    lib.sg_truth_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _engine = lib
     return lib
 
@@ -239,6 +262,8 @@ def load_host():
     lib.simu_prepare_batch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
     lib.simu_get_stats.argtypes = [vp, C.POINTER(SimuStats)]
     lib.simu_get_stats.restype = None
+    lib.simu_batch_slots.argtypes = [vp]
+    lib.simu_batch_slots.restype = C.c_uint64
     _host = lib
     return lib
 
@@ -313,6 +338,22 @@ def train_profile(ref: str, vcf: str, output: str, sam: str = "", bam: str = "",
     return st
 
 
+def truth_align(pieces, tmpl_off: int, tmpl_len: int, reverse: bool, events=(), cap: int = 512):
+    """sg_truth_align (host only, no GPU): the true alignment of a template of `tmpl_len` chain bases at `tmpl_off`.
+    `pieces`: (dst, src, len, contig, kind, seg_first) of the chain in offset order; `events`: ev_pack words in read
+    direction.  Returns (contig, pos0, [(len, op)]); contig -1 and no operations for an unmapped read."""
+    lib = load_engine()
+    arr = (SgTruthPiece * len(pieces))(*[SgTruthPiece(*p) for p in pieces])
+    ev = (C.c_uint32 * max(len(events), 1))(*events)
+    contig, pos0, n_ops = C.c_int32(), C.c_int64(), C.c_uint32()
+    cigar = (C.c_uint32 * cap)()
+    rc = lib.sg_truth_align(arr, len(pieces), tmpl_off, tmpl_len, 1 if reverse else 0, ev, len(events), C.byref(contig), C.byref(pos0),
+                            cigar, cap, C.byref(n_ops))
+    if rc != 0:
+        raise SimuError(f"sg_truth_align failed (code {rc})")
+    return contig.value, pos0.value, [(cigar[i] >> 4, cigar[i] & 15) for i in range(n_ops.value)]
+
+
 def release_cached_memory() -> None:
     """Device blocks that finished contexts left with the process go back to the runtime (sg_release_cached_memory)."""
     load_engine().sg_release_cached_memory()
@@ -361,6 +402,11 @@ class Session:
         self._check(self.lib.simu_prepare_batch(self._h, popu, chrom, C.byref(hw), self._err, len(self._err)))
         return bool(hw.value)
 
+    @property
+    def batch_slots(self) -> int:
+        """Planned fragment slots of the prepared batch: truth_reads addresses the reads by slot."""
+        return int(self.lib.simu_batch_slots(self._h))
+
     def set_stream(self, stream_handle: int) -> None:
         self._sg(self.eng.sg_set_stream(self.ctx, C.c_void_p(stream_handle)), "sg_set_stream")
 
@@ -390,6 +436,38 @@ class Session:
         buf = C.create_string_buffer(max(nbytes, 1))
         self._sg(self.eng.sg_fetch_compressed(self.ctx, mate, offset, nbytes, buf), "sg_fetch_compressed")
         return buf.raw[:nbytes]
+
+    # ---- truth alignments (sessions opened with truth_bam=1: the driver hands the piece map to the engine) ----
+    def truth_pieces(self, chain: int):
+        """The chain's copy list sorted by offset: (dst, src, len, contig, kind, seg_first) rows for truth_align."""
+        n = C.c_uint64()
+        self.eng.sg_truth_pieces(self.ctx, chain, None, 0, C.byref(n))
+        arr = (SgTruthPiece * max(n.value, 1))()
+        self._sg(self.eng.sg_truth_pieces(self.ctx, chain, arr, n.value, C.byref(n)), "sg_truth_pieces")
+        return [(p.dst, p.src, p.len, p.contig, p.kind, p.seg_first) for p in arr[:n.value]]
+
+    def truth_reads(self, mate: int, first_slot: int, n: int):
+        """Where reads [first_slot, first_slot + n) of mate 0 / 1 of the last pass came from: SgTruthRead rows."""
+        arr = (SgTruthRead * max(n, 1))()
+        self._sg(self.eng.sg_truth_reads(self.ctx, mate, first_slot, n, arr), "sg_truth_reads")
+        return arr
+
+    def truth_bam(self):
+        """Build the pass's BAM records and their BGZF members on the device; returns (record bytes, BGZF bytes)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._sg(self.eng.sg_truth_bam(self.ctx, C.byref(a), C.byref(b)), "sg_truth_bam")
+        return a.value, b.value
+
+    def fetch_truth(self, compressed: bool, nbytes: int, offset: int = 0) -> bytes:
+        buf = C.create_string_buffer(max(nbytes, 1))
+        self._sg(self.eng.sg_fetch_truth(self.ctx, 1 if compressed else 0, offset, nbytes, buf), "sg_fetch_truth")
+        return buf.raw[:nbytes]
+
+    def truth_info(self):
+        """(records, unmapped records) of the last truth_bam()."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._sg(self.eng.sg_truth_info(self.ctx, C.byref(a), C.byref(b)), "sg_truth_info")
+        return a.value, b.value
 
     def emit_info(self):
         """(items handed to the generic item code, whether the batch was re-emitted) of the last pass."""

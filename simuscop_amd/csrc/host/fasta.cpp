@@ -34,16 +34,18 @@ static std::string plain_path(const std::string& ref_file) {
   return path;
 }
 
-static std::string header_key(const std::string& header, bool crlf_as_lf) {  // Fasta.cpp:58-69
+static std::string header_token(const std::string& header, const char* stops) {
   size_t b = header.find_first_not_of(" \t");
-  std::string tok;
-  if (b != std::string::npos) {
-    // (the reference cuts the name at blanks and tabs only: the carriage return of a CR LF file stays in it)
-    size_t e = header.find_first_of(crlf_as_lf ? " \t\r" : " \t", b);
-    tok = header.substr(b, e == std::string::npos ? std::string::npos : e - b);
-  }
-  return abbr_of_chr(tok);
+  if (b == std::string::npos) return std::string();
+  size_t e = header.find_first_of(stops, b);
+  return header.substr(b, e == std::string::npos ? std::string::npos : e - b);
 }
+static std::string header_key(const std::string& header, bool crlf_as_lf) {  // Fasta.cpp:58-69
+  // (the reference cuts the name at blanks and tabs only: the carriage return of a CR LF file stays in it)
+  return abbr_of_chr(header_token(header, crlf_as_lf ? " \t\r" : " \t"));
+}
+// the contig's name as other tools read it from the file: the first token, no prefix cut, no carriage return
+static std::string header_written(const std::string& header) { return header_token(header, " \t\r"); }
 
 namespace {
 struct EngineError {};
@@ -66,7 +68,7 @@ std::string pread_string(int fd, uint64_t off, uint64_t n) {
 // a few small preads per contig -- header text, first line (bases / bytes per line), last bytes.  False when a
 // contig's body cannot be a run of equal-width lines.
 bool rows_from_headers(int fd, uint64_t size, const std::vector<uint64_t>& hdr, std::vector<std::string>& keys,
-                       std::vector<FastaContig>& rows, bool crlf_as_lf) {
+                       std::vector<std::string>& toks, std::vector<FastaContig>& rows, bool crlf_as_lf) {
   for (size_t i = 0; i < hdr.size(); i++) {
     const uint64_t region_end = i + 1 < hdr.size() ? hdr[i + 1] : size;
     // header line
@@ -124,6 +126,7 @@ bool rows_from_headers(int fd, uint64_t size, const std::vector<uint64_t>& hdr, 
     }
     if (!crlf_as_lf && head.find('\r') != std::string::npos) return false;
     keys.push_back(header_key(head, crlf_as_lf));
+    toks.push_back(header_written(head));
     rows.push_back(row);
   }
   return true;
@@ -140,7 +143,7 @@ bool Fasta::note_name(const std::string& key, bool seen) {
 void Fasta::open_on_device(const std::string& ref_file, sg_ctx* ctx, int threads) {
   const std::string path = plain_path(ref_file);
   on_device = true;
-  names.clear(); seqs.clear(); contigs.clear(); contig_of.clear();
+  names.clear(); seqs.clear(); contigs.clear(); contig_of.clear(); written.clear();
   int fd = ::open(path.c_str(), O_RDONLY);
   if (fd < 0) throw Error("could not open " + path);
   struct stat sb;
@@ -192,9 +195,9 @@ void Fasta::open_on_device(const std::string& ref_file, sg_ctx* ctx, int threads
     hdr.resize(found);
     std::sort(hdr.begin(), hdr.end());
     bool uniform = !(flags & 1u) && found > 0;
-    std::vector<std::string> keys;
+    std::vector<std::string> keys, toks;
     std::vector<FastaContig> rows;
-    if (uniform) uniform = rows_from_headers(fd, size, hdr, keys, rows, crlf_as_lf);
+    if (uniform) uniform = rows_from_headers(fd, size, hdr, keys, toks, rows, crlf_as_lf);
     if (uniform) {
       std::vector<sg_contig> tab;
       for (const FastaContig& r : rows) tab.push_back(sg_contig{r.raw_offset, r.length, r.line_bases, r.line_width});
@@ -206,6 +209,7 @@ void Fasta::open_on_device(const std::string& ref_file, sg_ctx* ctx, int threads
       contigs = rows;
       for (size_t i = 0; i < keys.size(); i++) {  // (a repeated name: listed again, resolved to its first sequence)
         if (!note_name(keys[i], contig_of.count(keys[i]) != 0)) contig_of[keys[i]] = (uint32_t)i;
+        written.emplace(keys[i], toks[i]);   // (emplace: the first header under a key names it)
       }
       streamed = true;
       ok = true;
@@ -257,6 +261,7 @@ void Fasta::open(const std::string& ref_file) {
   if (!fp) throw Error("could not open " + path);
   names.clear();
   seqs.clear();
+  written.clear();
   std::string* cur = nullptr;
   std::string ignored;   // the sequence under a repeated name is never read (note_name)
   std::vector<char> buf(1 << 22);
@@ -276,6 +281,7 @@ void Fasta::open(const std::string& ref_file) {
           in_header = false;
           std::string key = header_key(header, crlf_as_lf);
           cur = note_name(key, seqs.count(key) != 0) ? &ignored : &seqs[key];
+          written.emplace(key, header_written(header));
           cur->clear();
           header.clear();
         }
@@ -322,7 +328,7 @@ bool Fasta::load_index(const std::string& ref_file, int threads) {
   struct stat sb;
   if (fstat(fd, &sb) != 0) { ::close(fd); throw Error("could not open " + path); }
   const uint64_t size = (uint64_t)sb.st_size;
-  std::vector<std::string> keys;
+  std::vector<std::string> keys, toks;
   std::vector<FastaContig> rows;
   bool ok = false;
   // 1. a .fai next to the file: NAME LENGTH OFFSET LINEBASES LINEWIDTH (Fasta.cpp:45-85)
@@ -340,6 +346,7 @@ bool Fasta::load_index(const std::string& ref_file, int threads) {
         r.length = len; r.raw_offset = off; r.line_bases = (uint32_t)lb; r.line_width = (uint32_t)lw;
         if (off + len + (len ? (len - 1) / lb : 0) * (lw - lb) > size) { ok = false; break; }
         keys.push_back(abbr_of_chr(name));
+        toks.push_back(name);
         rows.push_back(r);
       }
       fclose(f);
@@ -375,7 +382,7 @@ bool Fasta::load_index(const std::string& ref_file, int threads) {
           if (pread(fd, &c, 1, (off_t)(end - 1)) != 1 || c == '\n' || c == '\r' || c == '>') { ok = false; break; }
         }
       }
-      if (!ok) { keys.clear(); rows.clear(); }
+      if (!ok) { keys.clear(); toks.clear(); rows.clear(); }
     }
   }
   // 2. header scan on the host: '>' at a line start; '@' headers and ';' comment lines are left to the general parser
@@ -416,7 +423,7 @@ bool Fasta::load_index(const std::string& ref_file, int threads) {
     bool plain = true;
     for (int t = 0; t < nt; t++) { plain &= !odd[(size_t)t]; hdr.insert(hdr.end(), found[(size_t)t].begin(), found[(size_t)t].end()); }
     std::sort(hdr.begin(), hdr.end());
-    ok = plain && !hdr.empty() && rows_from_headers(fd, size, hdr, keys, rows, crlf_as_lf);
+    ok = plain && !hdr.empty() && rows_from_headers(fd, size, hdr, keys, toks, rows, crlf_as_lf);
   }
   ::close(fd);
   if (ok) {   // a repeated name: ownership is by name, so such a file is ingested whole by every rank (open_on_device)
@@ -426,9 +433,10 @@ bool Fasta::load_index(const std::string& ref_file, int threads) {
   }
   if (!ok) return false;
   on_device = true;
-  names.clear(); seqs.clear(); contigs = rows; contig_of.clear(); dev_row.clear();
+  names.clear(); seqs.clear(); contigs = rows; contig_of.clear(); dev_row.clear(); written.clear();
   for (size_t i = 0; i < keys.size(); i++) {
     names.push_back(keys[i]);
+    written.emplace(keys[i], toks[i]);
     contig_of[keys[i]] = (uint32_t)i;
   }
   return true;

@@ -38,6 +38,10 @@ struct Fasta {
   bool on_device = false;
   std::vector<FastaContig> contigs;          // order of the table given to sg_reference_commit
   std::map<std::string, uint32_t> contig_of; // key -> row of `contigs`
+  // key -> the first token of its header line as the file writes it (`chr20` for the key `20`); of the first header
+  // under that key.  What the truth BAM's @SQ lines carry, so that they name the contigs as every other reader of the
+  // file does.
+  std::map<std::string, std::string> written;
   bool streamed = false;                     // false: the general host parser ran and its result was uploaded
   // sharded ingest (multi-GPU, ranks own whole contigs): every contig is in `names` / `contigs` with its length,
   // but only the owned ones are on this device; dev_row = row of the table given to sg_reference_commit, or -1

@@ -385,6 +385,7 @@ void Genome::segment_pieces(const std::string& popu, const std::string& chr, Seg
     g.hap_base[h] = plan.chain_len[h];
     g.hap_len[h] = size[h];
     uint64_t dst = plan.chain_len[h];
+    const size_t first_piece = plan.pieces.size();
     std::vector<std::pair<uint64_t, uint64_t>> s0_at;  // (S0 start of a kind-0 piece, its dst), ascending in both
     std::vector<uint64_t> s0_len;
     for (const Piece& p : table[h]) {
@@ -405,6 +406,8 @@ void Genome::segment_pieces(const std::string& popu, const std::string& chr, Seg
       dst += p.len;
     }
     plan.chain_len[h] = dst;
+    plan.piece_seg_first.resize(plan.pieces.size(), 0);
+    if (plan.pieces.size() > first_piece) plan.piece_seg_first[first_piece] = 1;
     for (const auto& kv : subs[h]) {  // a substituted base that was deleted afterwards is in no piece
       auto it = std::upper_bound(s0_at.begin(), s0_at.end(), std::pair<uint64_t, uint64_t>(kv.first, ~(uint64_t)0));
       if (it == s0_at.begin()) continue;
@@ -422,7 +425,7 @@ void Genome::build_chains(const std::string& popu, const std::string& chr, uint6
   const int ploidy = cfg.ploidy();
   plan.chains.assign(device_haps ? 0 : ploidy, std::string());
   plan.chain_len.assign(ploidy, 0);
-  plan.pieces.clear(); plan.patches.clear(); plan.literals.clear();
+  plan.pieces.clear(); plan.piece_seg_first.clear(); plan.patches.clear(); plan.literals.clear();
   const uint32_t ctx = host_ctx(popu, chr);
   const long clen = fa.length(chr);
   std::vector<std::string> haps;

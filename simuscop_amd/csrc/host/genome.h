@@ -56,6 +56,7 @@ struct ChromPlan {  // one (population, chromosome)
   // device haplotypes: the chains as copy lists for sg_build_haplotypes
   std::vector<uint64_t> chain_len;
   std::vector<sg_hap_piece> pieces;
+  std::vector<uint8_t> piece_seg_first;  // per piece: 1 on the first piece of a segment's haplotype string (sg_truth_map)
   std::vector<sg_hap_patch> patches;
   std::string literals;
   bool chains_built = false, windows_built = false, weighed = false;

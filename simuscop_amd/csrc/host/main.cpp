@@ -1,6 +1,7 @@
 // host/main.cpp -- `simuReads <configuration file>` (src/simuReads.cpp:24-97), GPU-backed.
 // Same positional argument, usage text and exit codes; optional flags are additive:
 //   --seed N  --device D  --out DIR  --no-write [--fetch]  --quiet  --rank R --world W  --stats  --host-haplotypes  --gzip
+//   --truth-bam   every read's true alignment as <stem>.truth.bam beside the FASTQ files (simulate.h)
 //   --gpus N [--shard-contigs]
 //   --crlf-as-lf  --strict-bases  --unique-contigs   (each turns one kept reference quirk off: simulate.h)
 #include <dirent.h>
@@ -79,7 +80,8 @@ static int pipe_exchange(void* user, double* values, int32_t n) {
 }
 
 static int run_on_gpus(int gpus, int base_device, const std::vector<std::string>& args, const std::string& self,
-                       const std::string& config, const std::string& out_override, bool merge, bool shard_contigs, bool gzip) {
+                       const std::string& config, const std::string& out_override, bool merge, bool shard_contigs, bool gzip,
+                       bool truth_bam) {
   // A profiler's preloaded tool library initialises the GPU before main(): exec'ing the children from here would then be
   // an exec from a GPU-initialised process.  Profile one rank directly instead (`simuReads cfg --rank r --world N`).
   const char* preload = getenv("LD_PRELOAD");
@@ -119,7 +121,7 @@ static int run_on_gpus(int gpus, int base_device, const std::vector<std::string>
         for (int q = 0; q < r; q++) { close(from_child[(size_t)q]); close(to_child[(size_t)q]); }
         a.insert(a.end(), {"--shard-contigs", "--exchange-fds", std::to_string(up[1]) + "," + std::to_string(down[0])});
       }
-      if (gzip && merge) a.push_back("--no-eof-block");
+      if ((gzip || truth_bam) && merge) a.push_back("--no-eof-block");
       if (r > 0) a.push_back("--quiet");
       std::vector<char*> cv;
       cv.push_back(const_cast<char*>(self.c_str()));
@@ -184,7 +186,8 @@ static int run_on_gpus(int gpus, int base_device, const std::vector<std::string>
       fclose(src);
       unlink(path.c_str());
     }
-    if (gzip) {  // one BGZF end-of-file block for the whole file (the parts were written without theirs)
+    const bool is_truth = base.size() > 10 && base.compare(base.size() - 10, 10, ".truth.bam") == 0;
+    if (gzip || (truth_bam && is_truth)) {  // one BGZF end-of-file block for the whole file (the parts were written without theirs)
       uint8_t eof[28];
       sg_bgzf_eof(eof);
       fwrite(eof, 1, 28, dst);
@@ -223,6 +226,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--stats") stats = true;
     else if (a == "--host-haplotypes") opt.host_haplotypes = 1;
     else if (a == "--gzip") opt.gzip = 1;
+    else if (a == "--truth-bam") opt.truth_bam = 1;
     else if (a == "--shard-contigs") opt.shard_contigs = 1;
     else if (a == "--no-eof-block") opt.no_eof_block = 1;
     else if (a == "--crlf-as-lf") opt.crlf_as_lf = 1;
@@ -255,7 +259,7 @@ int main(int argc, char* argv[]) {
     if (n <= 0) { std::cerr << "Error: cannot locate the executable for --gpus" << std::endl; return 1; }
     self[n] = 0;
     return run_on_gpus(gpus, opt.device >= 0 ? opt.device : 0, pass, self, config, out, opt.write_files != 0, opt.shard_contigs != 0,
-                       opt.gzip != 0);
+                       opt.gzip != 0, opt.truth_bam != 0);
   }
   time_t start_t = time(NULL);
   simu_stats st;
@@ -271,13 +275,15 @@ int main(int argc, char* argv[]) {
   if (stats)
     fprintf(stderr,
             "stats: reads=%llu fragments=%llu bytes=%llu windows=%llu segments=%llu batches=%llu | load %.3fs (engine %.3fs reference %.3fs) haplotypes %.3fs "
-            "plan %.3fs sample %.3fs (haplotype calls %.3fs sg_plan %.3fs) fetch %.3fs write %.3fs total %.3fs | kernels ms: plan %.3f namebase %.3f indel %.3f scan %.3f emit %.3f emit_slow %.3f | queued_items=%llu requeued_batches=%llu emit_kernel=%d slow_rows_lds=%d emit_lds=%u clean_cap=%u | compress %.3fs gz_bytes=%llu\n",
+            "plan %.3fs sample %.3fs (haplotype calls %.3fs sg_plan %.3fs) fetch %.3fs write %.3fs total %.3fs | kernels ms: plan %.3f namebase %.3f indel %.3f scan %.3f emit %.3f emit_slow %.3f | queued_items=%llu requeued_batches=%llu emit_kernel=%d slow_rows_lds=%d emit_lds=%u clean_cap=%u | compress %.3fs gz_bytes=%llu | "
+            "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f\n",
             (unsigned long long)st.reads, (unsigned long long)st.fragments, (unsigned long long)st.fastq_bytes,
             (unsigned long long)st.windows, (unsigned long long)st.segments, (unsigned long long)st.batches, st.t_load,
             st.t_engine, st.t_reference,
             st.t_haplotypes, st.t_plan, st.t_sample, st.t_hap_device, st.t_plan_api, st.t_fetch, st.t_write, st.t_total, st.kernel_ms[0], st.kernel_ms[1],
             st.kernel_ms[2], st.kernel_ms[3], st.kernel_ms[4], st.kernel_ms[5], (unsigned long long)st.queued_items,
             (unsigned long long)st.requeued_batches, st.emit_kernel, st.emit_slow_rows_lds, st.emit_lds_bytes,
-            st.emit_clean_cap, st.t_compress, (unsigned long long)st.gz_bytes);
+            st.emit_clean_cap, st.t_compress, (unsigned long long)st.gz_bytes, (unsigned long long)st.truth_records,
+            (unsigned long long)st.truth_unmapped, (unsigned long long)st.truth_bytes, (unsigned long long)st.truth_bgzf_bytes, st.t_truth);
   return 0;
 }

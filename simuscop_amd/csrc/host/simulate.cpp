@@ -52,7 +52,13 @@ struct Engine {  // RAII around sg_ctx, turns status codes into simu::Error
 struct Sink {  // FASTQ output: <output>/<stem>_1.fq + _2.fq, or <stem>.fq (Genome.cpp:857-866)
   FILE* f1 = nullptr;
   FILE* f2 = nullptr;
-  bool bgzf = false, eof_block = true;
+  FILE* ft = nullptr;   // <stem>.truth.bam (--truth-bam): BGZF whatever the FASTQ files are
+  bool bgzf = false, eof_block = true, truth_eof_block = true;
+  void open_truth(const std::string& dir, const std::string& stem, const std::string& suffix0) {
+    const std::string a = dir + "/" + stem + ".truth.bam" + suffix0;
+    ft = fopen(a.c_str(), "wb");
+    if (!ft) throw Error("Error: can not open BAM file to save the true alignments:\n" + a, -1);
+  }
   void open(const std::string& dir, const std::string& stem, bool paired, const std::string& suffix0, bool gz = false) {
     close();
     bgzf = gz;
@@ -76,9 +82,15 @@ struct Sink {  // FASTQ output: <output>/<stem>_1.fq + _2.fq, or <stem>.fq (Geno
       if (f1) fwrite(eof, 1, 28, f1);
       if (f2) fwrite(eof, 1, 28, f2);
     }
+    if (ft && truth_eof_block) {
+      uint8_t eof[28];
+      sg_bgzf_eof(eof);
+      fwrite(eof, 1, 28, ft);
+    }
     if (f1) fclose(f1);
     if (f2) fclose(f2);
-    f1 = f2 = nullptr;
+    if (ft) fclose(ft);
+    f1 = f2 = ft = nullptr;
   }
   ~Sink() { close(); }
 };
@@ -108,6 +120,86 @@ struct Driver {
   }
   void log(const std::string& s) { if (!opt.quiet) std::cerr << s; }
 
+  // ---- --truth-bam ----
+  // The header's references: the FASTA's contigs in file order, each under the first token of its header line as the
+  // file writes it (`chr20` stays `chr20`, although the reads' names and the variant files say `20`), so that the BAM
+  // and the FASTA name a contig alike.  A contig whose key the file holds twice (the same name again, or `chr20` and
+  // `20`): no read comes from the second sequence and SAM wants every SN once, so only the first is listed (fasta.h;
+  // --unique-contigs refuses such a file).
+  std::vector<std::pair<std::string, uint64_t>> truth_refs() const {
+    std::vector<std::string> name(genome.fa.contigs.size());
+    for (const auto& kv : genome.fa.contig_of) {
+      auto w = genome.fa.written.find(kv.first);
+      name[kv.second] = w == genome.fa.written.end() || w->second.empty() ? kv.first : w->second;
+    }
+    std::vector<std::pair<std::string, uint64_t>> out;
+    for (size_t r = 0; r < name.size(); r++)
+      if (!name[r].empty()) out.emplace_back(name[r], genome.fa.contigs[r].length);
+    return out;
+  }
+  // engine contig (row of the table given to sg_reference_commit) -> refID
+  std::vector<int32_t> truth_ref_ids() const {
+    std::vector<std::string> name(genome.fa.contigs.size());
+    for (const auto& kv : genome.fa.contig_of) name[kv.second] = kv.first;
+    std::vector<int32_t> ids;
+    int32_t next = 0;
+    for (size_t r = 0; r < name.size(); r++) {
+      const int32_t id = name[r].empty() ? -1 : next++;
+      const int32_t dev = genome.fa.dev_row.empty() ? (int32_t)r : genome.fa.dev_row[r];
+      if (dev < 0) continue;
+      if ((size_t)dev >= ids.size()) ids.resize((size_t)dev + 1, 0);
+      ids[(size_t)dev] = id < 0 ? 0 : id;
+    }
+    return ids;
+  }
+  // magic, header text, reference list (SAMv1 section 4.2) as BGZF members of their own, made by the device compressor
+  void write_truth_header(FILE* f) {
+    std::string text = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
+    const auto refs = truth_refs();
+    for (const auto& r : refs) text += "@SQ\tSN:" + r.first + "\tLN:" + std::to_string(r.second) + "\n";
+    text += "@PG\tID:simuReads\n";
+    std::string h("BAM\1", 4);
+    auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; i++) h.push_back((char)(v >> (8 * i))); };
+    put32((uint32_t)text.size());
+    h += text;
+    put32((uint32_t)refs.size());
+    for (const auto& r : refs) {
+      put32((uint32_t)r.first.size() + 1);
+      h += r.first;
+      h.push_back('\0');
+      put32((uint32_t)r.second);
+    }
+    std::vector<uint8_t> gz(h.size() + h.size() / 2 + 1024 * (h.size() / 32768 + 2));
+    uint64_t n = 0;
+    eng.check(sg_deflate_bgzf(eng.ctx, h.data(), h.size(), gz.data(), gz.size(), &n), "sg_deflate_bgzf");
+    if (fwrite(gz.data(), 1, n, f) != n) throw Error("Error: short write to the truth BAM file", -1);
+  }
+  std::vector<uint8_t> truth_host;
+  // the records of the pass just sampled: made, compressed, counted and (unless --no-write) appended to the file.
+  // Synchronous: the members are in the context's own buffer, which the next piece reuses.
+  void truth_piece(Sink& sink) {
+    auto t0 = Clock::now();
+    uint64_t rb = 0, gb = 0, nrec = 0, nun = 0;
+    eng.check(sg_truth_bam(eng.ctx, &rb, &gb), "sg_truth_bam");
+    eng.check(sg_truth_info(eng.ctx, &nrec, &nun), "sg_truth_info");
+    st.truth_records += nrec;
+    st.truth_unmapped += nun;
+    st.truth_bytes += rb;
+    st.truth_bgzf_bytes += gb;
+    if (opt.write_files && sink.ft && gb) {
+      if (truth_host.size() < gb) truth_host.resize(gb);
+      eng.check(sg_fetch_truth(eng.ctx, 1, 0, gb, truth_host.data()), "sg_fetch_truth");
+      if (fwrite(truth_host.data(), 1, gb, sink.ft) != gb) throw Error("Error: short write to the truth BAM file", -1);
+    }
+    st.t_truth += since(t0);
+  }
+  void open_sink(const std::string& dir, const std::string& stem, bool paired, const std::string& suffix) {
+    sink.open(dir, stem, paired, suffix, opt.gzip != 0);
+    if (!opt.truth_bam) return;
+    sink.open_truth(dir, stem, suffix);
+    if (opt.shard_world <= 1 || opt.shard_rank == 0) write_truth_header(sink.ft);
+  }
+
   void upload(const std::string& popu, const std::string& chr) {
     const std::string key = popu + "\t" + chr;
     if (resident == key) return;
@@ -119,6 +211,11 @@ struct Driver {
                                     plan.pieces.size(), plan.literals.data(), plan.literals.size(), plan.patches.data(),
                                     plan.patches.size()),
                 "sg_build_haplotypes");
+      if (opt.truth_bam) {  // the copy list is the reads' way back to the reference: contig rows -> refIDs of the BAM header
+        const std::vector<int32_t> ref_ids = truth_ref_ids();
+        eng.check(sg_truth_map(eng.ctx, plan.pieces.data(), plan.piece_seg_first.data(), plan.piece_seg_first.size(), ref_ids.data(), (uint32_t)ref_ids.size()),
+                  "sg_truth_map");
+      }
     } else {
       std::vector<const char*> ptr;
       std::vector<uint64_t> len;
@@ -530,6 +627,7 @@ struct Driver {
     st.fragments += nf;
     st.reads += paired ? 2 * nf : nf;
     st.fastq_bytes += n1 + n2;
+    if (opt.truth_bam) truth_piece(sink);
     if (!(opt.write_files || opt.fetch)) return;
     bool compressed = false;
     if (opt.gzip) {
@@ -657,6 +755,9 @@ struct Driver {
   void open(const std::string& config_path) {
     t_all = Clock::now();
     auto t0 = Clock::now();
+    if (opt.truth_bam && opt.host_haplotypes)
+      throw Error("Error: --truth-bam needs the haplotypes assembled on the device (their copy lists map the reads back to the "
+                  "reference); it cannot be combined with --host-haplotypes");
     cfg.load(config_path);
     seed = opt.has_seed ? opt.seed : (uint64_t)cfg.num["seed"];
     const int device = opt.device >= 0 ? opt.device : (int)cfg.num["device"];
@@ -724,8 +825,9 @@ struct Driver {
     const bool paired = cfg.paired();
     const std::string suffix = opt.shard_world > 1 ? ".part" + std::to_string(opt.shard_rank) : "";
     sink.eof_block = !opt.no_eof_block;
+    sink.truth_eof_block = !opt.no_eof_block && (opt.shard_world <= 1 || opt.shard_rank == opt.shard_world - 1);
     if (genome.mix_props.empty()) {
-      if (opt.write_files) sink.open(out_dir, popus[0], paired, suffix, opt.gzip != 0);
+      if (opt.write_files) open_sink(out_dir, popus[0], paired, suffix);
       set_read_counts(popus[0], reads);
       for (const std::string& chr : genome.chromosomes) run_batch(popus[0], chr, sink);
     } else {
@@ -739,7 +841,7 @@ struct Driver {
           stem += buf;
         }
         drain_wait();  // the previous mixture's last batch still writes into the files about to be closed
-        if (opt.write_files) sink.open(out_dir, stem, paired, suffix, opt.gzip != 0);
+        if (opt.write_files) open_sink(out_dir, stem, paired, suffix);
         for (size_t i = 0; i < popus.size(); i++) {
           const long popu_reads = (long)(reads * props[i] * acn[popus[i]] / w_acn);  // long*float is a float product (Genome.cpp:935)
           set_read_counts(popus[i], popu_reads);
@@ -901,3 +1003,10 @@ extern "C" int simu_prepare_batch(simu_session* s, int popu, int chr, int* has_w
   });
 }
 extern "C" void simu_get_stats(simu_session* s, simu_stats* st) { if (s && st) *st = s->d.st; }
+// planned fragment slots of the batch simu_prepare_batch handed to the engine (this shard's part)
+extern "C" uint64_t simu_batch_slots(simu_session* s) {
+  if (!s) return 0;
+  uint64_t n = 0;
+  for (size_t i = s->d.cur.a0; i < s->d.cur.a1 && i < s->d.cur.act.size(); i++) n += s->d.cur.act[i].slots;
+  return n;
+}

@@ -39,6 +39,10 @@ typedef struct simu_options {
                            //    holder of the short contexts, Profile.cpp:94-101, 220-226)
   int32_t unique_contigs;  // 1: refuse a FASTA that holds a contig name twice (default: the name stands twice in the
                            //    chromosome list and both resolve to the first sequence, Fasta.cpp:67,84-97,198)
+  int32_t truth_bam;       // 1: write every read's true alignment to <stem>.truth.bam beside the FASTQ files (sg_truth_bam: the
+                           //    records are made and compressed on the device, piece by piece, in FASTQ order); needs the
+                           //    device-assembled haplotypes (refused with host_haplotypes).  Sharded runs write parts like the
+                           //    FASTQ parts: rank 0's carries the header, the last rank's the BGZF end-of-file block
 } simu_options;
 
 typedef struct simu_stats {
@@ -66,6 +70,11 @@ typedef struct simu_stats {
   int32_t emit_kernel;     // the emit kernels of the last pass (sg_emit_path: SG_EMIT_*; 0: no pass ran)
   int32_t emit_slow_rows_lds;
   uint32_t emit_lds_bytes, emit_clean_cap;
+  uint64_t truth_records;  // truth_bam: BAM records made (one per read), of which without an alignment ...
+  uint64_t truth_unmapped;
+  uint64_t truth_bytes;    // ... bytes of the record stream and of its BGZF members (header and end-of-file block aside)
+  uint64_t truth_bgzf_bytes;
+  double t_truth;          // sg_truth_bam calls + fetching and writing their members (synchronous, per piece)
 } simu_stats;
 
 // Returns 0 on success.  On failure returns the exit code the reference would use and writes the
@@ -95,6 +104,7 @@ int simu_weighted_length(simu_session* s, int popu, double* wl, char* err, size_
 int simu_set_reads(simu_session* s, int popu, int64_t reads, char* err, size_t err_len);
 int simu_prepare_batch(simu_session* s, int popu, int chr, int* has_work, char* err, size_t err_len);
 void simu_get_stats(simu_session* s, simu_stats* st);
+uint64_t simu_batch_slots(simu_session* s);  // planned fragment slots of the prepared batch (sg_truth_reads addresses reads by slot)
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
 #include "sg_api.h"
 #include "sg_deflate.h"
 #include "sg_tables.h"
+#include "sg_truth.h"
 
 namespace {
 
@@ -712,6 +713,7 @@ int sg_detach_outputs(sg_ctx* ctx, sg_outputs** out) {
   ctx->results_valid = false;
   ctx->sampled = false;
   ctx->gz_valid = false;
+  ctx->truth.valid = false;
   *out = o;
   return SG_OK;
 }
@@ -920,6 +922,232 @@ int sg_fetch_compressed(sg_ctx* ctx, int mate, uint64_t offset, uint64_t bytes, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// truth alignments (rule: sg_truth.h, kernels: sg_truth.hip)
+// ------------------------------------------------------------------------------------------------
+int sg_truth_align(const sg_truth_piece* pieces, uint64_t n_pieces, uint64_t tmpl_off, uint32_t tmpl_len, int reverse,
+                   const uint32_t* events, uint32_t n_events, int32_t* contig, int64_t* pos0, uint32_t* cigar, uint32_t cap,
+                   uint32_t* n_ops) {
+  if (!pieces || !n_pieces || !contig || !pos0 || !n_ops || (cap && !cigar) || (n_events && !events) || n_events > SG_MAX_EVENTS ||
+      tmpl_len == 0 || tmpl_len > 0xFFFFu)
+    return SG_ERR_INVALID;
+  std::vector<sg::TruthPiece> tp((size_t)n_pieces);
+  for (uint64_t i = 0; i < n_pieces; i++) {
+    const sg_truth_piece& p = pieces[i];
+    if (p.len == 0 || p.contig > 0x3FFFFFFFu || (i && p.dst != pieces[i - 1].dst + pieces[i - 1].len)) return SG_ERR_INVALID;
+    tp[i] = sg::TruthPiece{p.dst, p.src, p.len, sg::truth_meta(p.contig, p.kind, p.seg_first)};
+  }
+  if (tmpl_off < tp[0].dst || tmpl_off + tmpl_len > tp.back().dst + tp.back().len) return SG_ERR_INVALID;
+  uint32_t next = 0;   // events ascend and stay apart: a deletion of [j, j + k) is followed by j + k at the earliest
+  for (uint32_t e = 0; e < n_events; e++) {
+    const uint32_t j = events[e] & 0xFFFFu, k = (events[e] >> 16) & 0x7FFFu, del = events[e] >> 31;
+    if (k == 0 || j < next || j >= tmpl_len || (del && j + k > tmpl_len)) return SG_ERR_INVALID;
+    next = del ? j + k : j + 1;
+  }
+  const uint64_t pi = sg::truth_find_piece(tp.data(), 0, n_pieces, tmpl_off);
+  const sg::TruthAln A = sg::truth_walk(tp.data(), n_pieces, pi, tmpl_off, tmpl_len, reverse != 0, events, n_events,
+                                        [&](uint32_t i, uint32_t v) { if (i < cap) cigar[i] = v; });
+  *contig = A.contig;
+  *pos0 = A.pos0;
+  *n_ops = A.n_ops;
+  return A.n_ops > cap ? SG_ERR_OVERFLOW : SG_OK;
+}
+
+static int truth_need_map(sg_ctx* ctx, const char* who) {
+  if (!ctx->truth.from_build)
+    return ctx->fail(SG_ERR_INVALID, std::string(who) + ": the chains have no piece map (they were not made by sg_build_haplotypes)");
+  if (!ctx->truth.mapped) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_truth_map first");
+  return SG_OK;
+}
+
+int sg_truth_map(sg_ctx* ctx, const sg_hap_piece* pieces, const uint8_t* seg_first, uint64_t n_pieces, const int32_t* ref_ids,
+                 uint32_t n_ref_ids) {
+  if (!ctx || (n_pieces && (!pieces || !seg_first))) return SG_ERR_INVALID;
+  sg_ctx::Truth& T = ctx->truth;
+  if (!T.from_build || !ctx->have_haps)
+    return ctx->fail(SG_ERR_INVALID, "sg_truth_map: the chains have no piece map (they were not made by sg_build_haplotypes)");
+  if (n_pieces != T.n_given) return ctx->fail(SG_ERR_INVALID, "sg_truth_map: the pieces are not those of sg_build_haplotypes (another count)");
+  SG_HIP(hipSetDevice(ctx->device));
+  const size_t n_chains = ctx->hap.len.size();
+  for (uint64_t i = 0; i < n_pieces; i++)
+    if (pieces[i].chain >= n_chains) return ctx->fail(SG_ERR_INVALID, "sg_truth_map: piece " + std::to_string(i) + " names a chain that does not exist");
+  std::vector<uint64_t> order((size_t)n_pieces);
+  for (uint64_t i = 0; i < n_pieces; i++) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    const sg_hap_piece &x = pieces[a], &y = pieces[b];
+    return x.chain != y.chain ? x.chain < y.chain : x.dst < y.dst;
+  });
+  // Everything is checked and built beside the context's state, which changes only once nothing can fail any more: a
+  // refused call leaves an earlier map as it was.  The pieces of a chain must tile it -- no hole, no overlap, none of
+  // length 0 (the walk of sg_truth.h takes a piece's first base for granted).
+  std::vector<sg_truth_piece> sorted((size_t)n_pieces);
+  std::vector<uint64_t> chain_first(n_chains + 1, n_pieces);
+  std::vector<sg::TruthPiece> dev((size_t)n_pieces);
+  uint32_t chain = 0;
+  uint64_t at = 0;   // offset in `chain` up to which it is tiled
+  chain_first[0] = 0;
+  auto chain_done = [&]() { return at == ctx->hap.len[chain]; };
+  for (uint64_t i = 0; i < n_pieces; i++) {
+    const sg_hap_piece& p = pieces[order[i]];
+    while (chain < p.chain) {
+      if (!chain_done()) return ctx->fail(SG_ERR_INVALID, "sg_truth_map: the pieces of chain " + std::to_string(chain) + " do not tile it");
+      chain_first[++chain] = i;
+      at = 0;
+    }
+    if (p.len == 0 || p.dst != at)
+      return ctx->fail(SG_ERR_INVALID, "sg_truth_map: the pieces of chain " + std::to_string(chain) + " do not tile it (piece " + std::to_string(order[i]) + ")");
+    at += p.len;
+    sorted[i] = sg_truth_piece{p.dst, p.src, p.len, p.contig, p.kind ? 1u : 0u, seg_first[order[i]] ? 1u : 0u};
+    int32_t ref = (int32_t)p.contig;
+    if (ref_ids && !p.kind) {
+      if (p.contig >= n_ref_ids) return ctx->fail(SG_ERR_INVALID, "sg_truth_map: a piece's contig has no entry in ref_ids");
+      ref = ref_ids[p.contig];
+    }
+    if (ref < 0 || ref > 0x3FFFFFFF) return ctx->fail(SG_ERR_INVALID, "sg_truth_map: reference id out of range");
+    dev[i] = sg::TruthPiece{p.dst, p.src, p.len, sg::truth_meta((uint32_t)ref, p.kind, seg_first[order[i]])};
+  }
+  for (;;) {
+    if (n_chains && !chain_done()) return ctx->fail(SG_ERR_INVALID, "sg_truth_map: the pieces of chain " + std::to_string(chain) + " do not tile it");
+    if (chain + 1 >= n_chains) break;
+    chain_first[++chain] = n_pieces;
+    at = 0;
+  }
+  T.mapped = false;   // (a copy that fails half-way leaves no map rather than a mixed one)
+  T.valid = false;
+  const size_t first_b = ((n_chains + 1) * 8 + 63) & ~(size_t)63;
+  SG_ENSURE(ctx->truth_map, first_b + dev.size() * sizeof(sg::TruthPiece) + 64);
+  SG_HIP(hipMemcpyAsync(ctx->truth_map.p, chain_first.data(), (n_chains + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (!dev.empty())
+    SG_HIP(hipMemcpyAsync(ctx->truth_map.as<uint8_t>() + first_b, dev.data(), dev.size() * sizeof(sg::TruthPiece), hipMemcpyHostToDevice, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));   // dev is host memory of this frame
+  T.sorted.swap(sorted);
+  T.chain_first.swap(chain_first);
+  T.mapped = true;
+  return SG_OK;
+}
+
+int sg_truth_pieces(sg_ctx* ctx, uint32_t chain, sg_truth_piece* out, uint64_t cap, uint64_t* n) {
+  if (!ctx || !n || (cap && !out)) return SG_ERR_INVALID;
+  if (int rc = truth_need_map(ctx, "sg_truth_pieces")) return rc;
+  const sg_ctx::Truth& T = ctx->truth;
+  if ((size_t)chain + 1 >= T.chain_first.size()) return ctx->fail(SG_ERR_INVALID, "sg_truth_pieces: chain index out of range");
+  const uint64_t a = T.chain_first[chain], b = T.chain_first[chain + 1];
+  *n = b - a;
+  if (b - a > cap) return ctx->fail(SG_ERR_OVERFLOW, "sg_truth_pieces: the pieces do not fit cap");
+  std::copy(T.sorted.begin() + (long)a, T.sorted.begin() + (long)b, out);
+  return SG_OK;
+}
+
+static_assert(sizeof(sg_truth_read) == sizeof(sg::TruthReadRow), "sg_truth_read is the kernel's row");
+
+int sg_truth_reads(sg_ctx* ctx, int mate, uint32_t first_slot, uint32_t n, sg_truth_read* out) {
+  if (!ctx || mate < 0 || mate > 1 || (n && !out)) return SG_ERR_INVALID;
+  if (int rc = truth_need_map(ctx, "sg_truth_reads")) return rc;
+  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_truth_reads: call sg_result first");
+  if (mate == 1 && !ctx->B.paired) return ctx->fail(SG_ERR_INVALID, "sg_truth_reads: a single-end pass has no mate 2");
+  if ((uint64_t)first_slot + n > ctx->B.n_slots) return ctx->fail(SG_ERR_INVALID, "sg_truth_reads: slots past the end of the batch");
+  if (!n) return SG_OK;
+  SG_HIP(hipSetDevice(ctx->device));
+  SG_ENSURE(ctx->truth_rows, (size_t)n * sizeof(sg::TruthReadRow));
+  sg::launch_truth_reads(ctx->P, ctx->B, (uint32_t)mate, first_slot, n, ctx->truth_rows.as<sg::TruthReadRow>(), ctx->stream);
+  SG_HIP(hipGetLastError());
+  SG_HIP(hipMemcpyAsync(out, ctx->truth_rows.p, (size_t)n * sizeof(sg::TruthReadRow), hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  return SG_OK;
+}
+
+int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
+  if (!ctx) return SG_ERR_INVALID;
+  if (int rc = truth_need_map(ctx, "sg_truth_bam")) return rc;
+  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam: call sg_result first");
+  SG_HIP(hipSetDevice(ctx->device));
+  sg_ctx::Truth& T = ctx->truth;
+  const sg::DevBatch& B = ctx->B;
+  const uint32_t nm = B.paired ? 2 : 1;
+  if ((uint64_t)B.n_slots * nm >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: more than 2^32 reads in one pass");
+  if (B.prefix_len > 200) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: read names longer than a BAM record holds");
+  if (B.diag) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: the pass ran under SG_DIAG (a timing ablation: its reads are not those of their rows)");
+  const uint32_t N = B.n_slots * nm;
+  T.valid = false;
+  T.rec_bytes = T.gz_bytes = T.records = T.unmapped = 0;
+  hipStream_t s = ctx->stream;
+  sg::TruthJob J;
+  memset(&J, 0, sizeof J);
+  const size_t first_b = ((ctx->hap.len.size() + 1) * 8 + 63) & ~(size_t)63;
+  J.chain_first = ctx->truth_map.as<uint64_t>();
+  J.pieces = (const sg::TruthPiece*)(ctx->truth_map.as<uint8_t>() + first_b);
+  J.n_chains = (uint32_t)ctx->hap.len.size();
+  J.n_reads = N;
+  // the pack kernel's stages: one record's FASTQ text and one record's image, for reads of up to L + 512 bases
+  const uint32_t np_cap = (uint32_t)ctx->P.L + 512u;
+  J.text_lds = (16u + 256u + 2u * np_cap + 4u + 31u) & ~15u;
+  J.image_lds = (16u + 36u + 256u + 4u * sg::kTruthMaxOps + np_cap + (np_cap + 1u) / 2u + 15u) & ~15u;
+  if ((size_t)sg::kTruthWaveOps * 4 + 64 * 9 * 4 + J.text_lds + J.image_lds > 160u * 1024u)
+    return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: reads too long for the record kernel");
+  // work buffer: counters (8 u64: records, unmapped, flags, -, stream bytes) | rows | rec_len | rec_off | block sums
+  const size_t off_rows = 64, off_len = off_rows + (size_t)N * sizeof(sg::TruthRow);
+  const size_t off_off = (off_len + (size_t)N * 4 + 63) & ~(size_t)63, off_bsum = off_off + (size_t)N * 8;
+  SG_ENSURE(ctx->truth_work, off_bsum + ((size_t)sg::scan_blocks(N) + 8) * 8);
+  uint8_t* wk = ctx->truth_work.as<uint8_t>();
+  J.counters = (unsigned long long*)wk;
+  J.rows = (sg::TruthRow*)(wk + off_rows);
+  J.rec_len = (uint32_t*)(wk + off_len);
+  J.rec_off = (const uint64_t*)(wk + off_off);
+  SG_HIP(hipMemsetAsync(wk, 0, 64, s));
+  uint64_t c[5] = {0, 0, 0, 0, 0};
+  if (N) {
+    sg::launch_truth_size(ctx->P, B, J, s);
+    sg::launch_scan_u32(J.rec_len, N, (uint64_t*)(wk + off_bsum), (uint64_t*)(wk + off_off), (uint64_t*)(wk + 32), s);
+    SG_HIP(hipGetLastError());
+    SG_HIP(hipMemcpyAsync(c, wk, sizeof c, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+  }
+  if (c[2] & 3) return ctx->fail(SG_ERR_OVERFLOW, "sg_truth_bam: an alignment with more than " + std::to_string(sg::kTruthMaxOps) + " operations");
+  const uint64_t total = c[4];
+  if (total) {
+    SG_ENSURE(ctx->truth_rec, total + 64);
+    J.out = ctx->truth_rec.as<uint8_t>();
+    J.out_bytes = total;
+    sg::launch_truth_pack(ctx->P, B, J, s);
+    SG_HIP(hipGetLastError());
+    uint64_t flags = 0;
+    SG_HIP(hipMemcpyAsync(&flags, wk + 16, 8, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    if (flags & 4) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: a record does not fit the record kernel's stages");
+    if (int rc = deflate_text(ctx, ctx->truth_rec.as<uint8_t>(), total, ctx->truth_gz, &T.gz_bytes, "sg_truth_bam")) return rc;
+  }
+  T.rec_bytes = total;
+  T.records = c[0];
+  T.unmapped = c[1];
+  T.valid = true;
+  if (record_bytes) *record_bytes = T.rec_bytes;
+  if (bgzf_bytes) *bgzf_bytes = T.gz_bytes;
+  return SG_OK;
+}
+
+int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes, void* host_dst) {
+  if (!ctx || (bytes && !host_dst)) return SG_ERR_INVALID;
+  if (int rc = truth_need_map(ctx, "sg_fetch_truth")) return rc;
+  if (!ctx->truth.valid) return ctx->fail(SG_ERR_INVALID, "sg_fetch_truth: call sg_truth_bam first");
+  if (offset + bytes > (compressed ? ctx->truth.gz_bytes : ctx->truth.rec_bytes)) return ctx->fail(SG_ERR_INVALID, "sg_fetch_truth: range past the end of the data");
+  SG_HIP(hipSetDevice(ctx->device));
+  if (bytes) {
+    const uint8_t* src = (compressed ? ctx->truth_gz : ctx->truth_rec).as<uint8_t>() + offset;
+    SG_HIP(hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return SG_OK;
+}
+
+int sg_truth_info(sg_ctx* ctx, uint64_t* records, uint64_t* unmapped) {
+  if (!ctx) return SG_ERR_INVALID;
+  if (int rc = truth_need_map(ctx, "sg_truth_info")) return rc;
+  if (!ctx->truth.valid) return ctx->fail(SG_ERR_INVALID, "sg_truth_info: call sg_truth_bam first");
+  if (records) *records = ctx->truth.records;
+  if (unmapped) *unmapped = ctx->truth.unmapped;
+  return SG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // reference ingest + haplotype assembly on the device (kernels: sg_haplotypes.hip)
 // ------------------------------------------------------------------------------------------------
 int sg_reference_begin(sg_ctx* ctx, uint64_t raw_bytes) {
@@ -1056,7 +1284,13 @@ int sg_build_haplotypes(sg_ctx* ctx, int32_t n_chains, const uint64_t* lens, con
   }
   sg::launch_hap_copy(ctx->chains.as<uint8_t>(), ctx->ref_codes.as<uint8_t>(), wk + pieces_b + patches_b, (const sg::DevPiece*)wk, dp.size(), ctx->stream);
   sg::launch_hap_patch(ctx->chains.as<uint8_t>(), (const sg::DevPatch*)(wk + pieces_b), pt.size(), ctx->stream);
-  return commit_chains(ctx, std::move(L));   // (synchronises: dp / pt are stack-owned host memory)
+  const int rc = commit_chains(ctx, std::move(L));   // (synchronises: dp / pt are stack-owned host memory)
+  ctx->truth = sg_ctx::Truth();
+  if (rc == SG_OK) {   // chains with a copy list: sg_truth_map may be given it (nothing of it is kept here)
+    ctx->truth.n_given = n_pieces;
+    ctx->truth.from_build = true;
+  }
+  return rc;
 }
 
 int sg_haplotype_codes(sg_ctx* ctx, uint32_t chain, uint64_t offset, uint64_t n, uint8_t* codes_out) {
@@ -1080,6 +1314,7 @@ int sg_upload_haplotypes(sg_ctx* ctx, int32_t n_chains, const char* const* chain
     if (lens[c]) SG_HIP(hipMemcpyAsync((uint8_t*)ctx->chains.p + L.off[c], chains[c], lens[c], hipMemcpyHostToDevice, ctx->stream));
   // ASCII -> base codes, in place (A0 C1 T2 G3, N=4, other=5): the kernels never see ASCII
   sg::launch_encode((uint8_t*)ctx->chains.p, L.total, ctx->stream);
+  ctx->truth = sg_ctx::Truth();   // strings have no copy list
   return commit_chains(ctx, std::move(L));
 }
 
@@ -1264,6 +1499,7 @@ int sg_sample(sg_ctx* ctx) {
   if (!ctx) return SG_ERR_INVALID;
   if (!ctx->have_plan) return ctx->fail(SG_ERR_INVALID, "sg_sample: call sg_plan first");
   SG_HIP(hipSetDevice(ctx->device));
+  ctx->truth.valid = false;
   return run_pass(ctx);
 }
 

@@ -60,6 +60,18 @@ struct sg_ctx {
   } hap;
   uint64_t gz_bytes[2] = {0, 0};
   bool gz_valid = false;
+  // truth alignments (sg_truth_*): whether the chains came from a copy list (sg_build_haplotypes; how many pieces it
+  // had) and, once sg_truth_map has been given that list, its pieces sorted by (chain, dst) with the chains' first
+  // indexes -- on the host for sg_truth_pieces, on the device (truth_map: chain_first, then sg::TruthPiece rows) for the
+  // record kernels.  Without sg_truth_map nothing is kept and nothing is allocated.
+  struct Truth {
+    uint64_t n_given = 0;
+    bool from_build = false, mapped = false, valid = false;
+    std::vector<sg_truth_piece> sorted;
+    std::vector<uint64_t> chain_first;
+    uint64_t rec_bytes = 0, gz_bytes = 0, records = 0, unmapped = 0;
+  } truth;
+  DevBuf truth_map, truth_work, truth_rec, truth_gz, truth_rows;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // device-made sampling plan: window weights per store id (sg_windows_build), the batch table of sg_plan_windows
   std::map<uint32_t, DevBuf> wstore;

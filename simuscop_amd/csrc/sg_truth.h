@@ -1,0 +1,193 @@
+// sg_truth.h -- truth alignments of the sampled reads (simuReads --truth-bam): the alignment rule, once, for the host
+// function sg_truth_align and for the record kernels of sg_truth.hip, and what those kernels share with the host API.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sg_device.h"
+
+namespace sg {
+
+// CIGAR operation codes of SAMv1 section 4.2
+enum : uint32_t { kOpM = 0, kOpI = 1, kOpD = 2, kOpN = 3, kOpS = 4 };
+
+// One entry of the piece map (sg_build_haplotypes' copy list, sorted by chain and offset): 24 bytes.
+struct TruthPiece {
+  uint64_t dst;    // offset in its chain
+  uint64_t src;    // kind 0: 0-based position on the contig
+  uint32_t len;
+  uint32_t meta;   // contig (BAM refID) | kind << 30 | seg_first << 31
+};
+__host__ __device__ inline uint32_t truth_meta(uint32_t contig, uint32_t kind, uint32_t seg_first) {
+  return (contig & 0x3FFFFFFFu) | ((kind ? 1u : 0u) << 30) | ((seg_first ? 1u : 0u) << 31);
+}
+
+// What the walk found: the alignment's contig, the position of its first and behind its last M base, its operations.
+struct TruthAln {
+  int32_t contig;
+  int64_t pos0, end;
+  uint32_t n_ops;
+};
+
+// The alignment rule (DESIGN.md "Truth alignments").  The template is `L` chain bases from `tmpl_off` on; `pieces` are
+// its chain's pieces in offset order, `pi` the index of the one that holds tmpl_off.  Events are in read direction
+// (ev_pack form): for a reverse read index j counts from the template's chain end.  The walk goes base by base in chain
+// direction and hands runs of operations to `put(index, len << 4 | op)`; what it hands over is already normalised:
+//   * before the first M base nothing is put: query bases met there (literal bases, inserted bases) are summed up and
+//     become one S in front of that M, gaps are dropped (the position is the first M base's);
+//   * operations behind an M run are put as they close; at the end everything behind the last M run is withdrawn
+//     (n_ops steps back: `put` may have been called for indexes that do not count) and its query bases become one S.
+// A read without an M base is unmapped: n_ops = 0, contig = -1.
+template <class Put>
+__host__ __device__ inline TruthAln truth_walk(const TruthPiece* pieces, uint64_t n_pieces, uint64_t pi, uint64_t tmpl_off, uint32_t L,
+                                               bool reverse, const uint32_t* events, uint32_t n_events, Put put) {
+  TruthAln A;
+  A.contig = -1; A.pos0 = -1; A.end = -1; A.n_ops = 0;
+  uint32_t n = 0, cur_op = kOpM, cur_len = 0, m_end = 0, lead_q = 0, q_since = 0;
+  bool seen_m = false;
+  auto unit = [&](uint32_t op, uint32_t len, int64_t refpos) {
+    if (!len) return;
+    if (!seen_m) {
+      if (op == kOpM) {
+        seen_m = true;
+        if (lead_q) put(n++, (lead_q << 4) | kOpS);
+        cur_op = kOpM; cur_len = len;
+        A.pos0 = refpos; A.end = refpos + len;
+      } else if (op == kOpI || op == kOpS) {
+        lead_q += len;
+      }
+      return;
+    }
+    if (op == cur_op) {
+      cur_len += len;
+    } else {
+      put(n++, (cur_len << 4) | cur_op);
+      if (cur_op == kOpM) m_end = n;
+      cur_op = op; cur_len = len;
+    }
+    if (op == kOpM) { q_since = 0; A.end = refpos + len; }
+    else if (op == kOpI || op == kOpS) q_since += len;
+  };
+
+  // the last reference piece walked through: where it ends on its contig; whether a segment began since
+  bool have_ref = false, broken = false, seg_began = false;
+  uint32_t ref_contig = 0;
+  uint64_t ref_next = 0;
+  int e = reverse ? (int)n_events - 1 : 0;   // next event in chain direction
+  uint32_t del_until = 0;
+  bool fresh = true;                          // the current piece has not been looked at yet
+  for (uint32_t c = 0; c < L; c++) {
+    const uint64_t at = tmpl_off + c;
+    while (pi + 1 < n_pieces && at >= pieces[pi].dst + pieces[pi].len) { pi++; fresh = true; }
+    const TruthPiece& p = pieces[pi];
+    const bool literal = (p.meta >> 30) & 1u;
+    if (fresh) {
+      fresh = false;
+      if (c > 0 && (p.meta >> 31)) seg_began = true;
+      if (!literal) {
+        const uint32_t contig = p.meta & 0x3FFFFFFFu;
+        const uint64_t here = p.src + (at - p.dst);
+        if (have_ref && !broken) {
+          if (contig != ref_contig || here < ref_next) broken = true;
+          else if (here > ref_next) unit(seg_began ? kOpN : kOpD, (uint32_t)(here - ref_next), 0);
+        }
+        have_ref = true;
+        ref_contig = contig;
+        ref_next = p.src + p.len;
+        seg_began = false;
+        if (!seen_m && !broken) A.contig = (int32_t)contig;
+      }
+    }
+    const uint32_t cls = broken ? kOpS : literal ? kOpI : kOpM;
+    const int64_t refpos = (int64_t)(p.src + (at - p.dst));
+    uint32_t ins_behind = 0;
+    if (!reverse) {
+      if (e < (int)n_events && (events[e] & 0xFFFFu) == c) {
+        const uint32_t k = (events[e] >> 16) & 0x7FFFu;
+        if (events[e] >> 31) del_until = c + k; else ins_behind = k;
+        e++;
+      }
+    } else if (e >= 0) {
+      const uint32_t j = events[e] & 0xFFFFu, k = (events[e] >> 16) & 0x7FFFu;
+      if (events[e] >> 31) {
+        if (L - j - k == c) { del_until = c + k; e--; }
+      } else if (L - 1u - j == c) {
+        unit(cls == kOpS ? kOpS : kOpI, k, 0);   // read direction: behind base j = in front of it on the chain
+        e--;
+      }
+    }
+    if (c < del_until) {
+      if (cls == kOpM) unit(kOpD, 1, refpos);
+    } else {
+      unit(cls, 1, refpos);
+    }
+    if (ins_behind) unit(cls == kOpS ? kOpS : kOpI, ins_behind, 0);
+  }
+  if (!seen_m) { A.contig = -1; A.pos0 = -1; A.end = -1; return A; }
+  if (cur_op == kOpM) {
+    put(n++, (cur_len << 4) | kOpM);
+  } else {
+    n = m_end;
+    if (q_since) put(n++, (q_since << 4) | kOpS);
+  }
+  A.n_ops = n;
+  return A;
+}
+
+// index of the piece of [first, last) that holds chain offset `off` (the pieces tile the chain)
+__host__ __device__ inline uint64_t truth_find_piece(const TruthPiece* pieces, uint64_t first, uint64_t last, uint64_t off) {
+  uint64_t lo = first, hi = last;   // the last piece with dst <= off
+  while (lo + 1 < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (pieces[mid].dst <= off) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// reg2bin of SAMv1 section 5.3 for [beg, end)
+__host__ __device__ inline uint32_t truth_reg2bin(int64_t beg, int64_t end) {
+  --end;
+  if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+  if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+  if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+  if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+  if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+
+constexpr uint32_t kTruthMaxOps = 256;     // CIGAR operations of one record (more: SG_ERR_OVERFLOW)
+constexpr uint32_t kTruthWaveOps = 2048;   // ... and of the 64 records one wave packs
+
+// Per read, in record order (index = slot * mates + mate): what the sizing kernel found.
+struct TruthRow {
+  int32_t contig;   // -1: unmapped
+  int32_t pos, end;
+  uint32_t n_ops;
+};
+
+struct TruthJob {
+  const TruthPiece* pieces;
+  const uint64_t* chain_first;   // [n_chains + 1] first piece of every chain
+  uint32_t n_chains;
+  uint32_t n_reads;              // n_slots * mates
+  TruthRow* rows;                // [n_reads]
+  uint32_t* rec_len;             // [n_reads] bytes of the record with its block_size word (0: unused slot)
+  const uint64_t* rec_off;       // [n_reads] exclusive scan of rec_len
+  unsigned long long* counters;  // [0] records, [1] unmapped, [2] flags: 1 a record with more than kTruthMaxOps operations, 2 a wave's records with more than kTruthWaveOps, 4 a record that does not fit the pack kernel's LDS
+  uint8_t* out;                  // the record stream
+  uint64_t out_bytes;
+  uint32_t text_lds;             // bytes of the pack kernel's text stage, image stage (multiples of 16)
+  uint32_t image_lds;
+};
+void launch_truth_size(const DevProfile& P, const DevBatch& B, const TruthJob& J, hipStream_t s);
+void launch_truth_pack(const DevProfile& P, const DevBatch& B, const TruthJob& J, hipStream_t s);
+// sg_truth_reads: the layout of sg_truth_read (simuscop_amd.h)
+struct TruthReadRow {
+  uint32_t live, chain, reverse, read_len;
+  uint64_t tmpl_off;
+  uint32_t n_events, inside;
+  uint32_t events[SG_MAX_EVENTS];
+};
+void launch_truth_reads(const DevProfile& P, const DevBatch& B, uint32_t mate, uint32_t first_slot, uint32_t n, TruthReadRow* out, hipStream_t s);
+
+}  // namespace sg
