@@ -378,6 +378,43 @@ int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes);
 int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes, void* host_dst);
 int sg_truth_info(sg_ctx* ctx, uint64_t* records, uint64_t* unmapped);
 
+/* ---- true coverage: the depth the reads of all passes really laid down (simuReads --truth-depth) -------------------
+ * Coverage adds up, so it needs no sort: one int32 difference array over the reference (len + 1 slots per contig, 4
+ * bytes per reference base) takes +1 / -1 for every M run of every read's true alignment (the rule above), pass after
+ * pass, population after population; a prefix sum at the end gives the depth.  A read counts at the reference positions
+ * of its M operations only (D, N, I, S and unmapped reads add nothing; both mates count where they overlap): the
+ * default of `samtools depth`.  Additive: a context that never calls sg_depth_begin launches no kernel of this part and
+ * holds no device memory for it; every call below before sg_depth_begin is SG_ERR_INVALID, and so is a contig index out
+ * of range.  Contigs are shorter than 2^32 - 8 bases (SG_ERR_UNSUPPORTED), depths are taken modulo 2^32.
+ *   sg_depth_begin      allocates and zeroes the array for contigs of these lengths (a second call replaces the state);
+ *                       SG_ERR_HIP with the size in the message when the device cannot hold it
+ *   sg_depth_add        after sg_result (and sg_truth_map): adds the current pass's reads; *m_bases = M bases added.  A
+ *                       run outside its contig is not written and the call fails with SG_ERR_INVALID.  Refuses a pass
+ *                       that ran under SG_DIAG, like sg_truth_bam
+ *   sg_depth_add_spans  adds spans [start, end) of contigs, given by the host; a span out of range or with start > end:
+ *                       SG_ERR_INVALID, and nothing is added
+ *   sg_depth_bins       sums[k] = 64-bit sum of the depths of bases [k * bin, min((k + 1) * bin, LN)); *n = number of bins.
+ *                       cap == 0 gives the count alone; SG_ERR_OVERFLOW when 0 < cap < *n
+ *   sg_depth_runs       maximal runs of equal depth as (start, depth) rows in order (a run ends where the next starts,
+ *                       the last at LN); cap as above
+ *   sg_depth_fetch      per-base depths of bases [first, first + n)
+ *   sg_depth_reset      zeroes the array and the count, keeps the buffers
+ *   sg_depth_info       contigs, M bases added since sg_depth_begin / sg_depth_reset, bases per tile of the finishing pass
+ *   sg_depth_end        frees everything                                                                              */
+typedef struct sg_depth_run {
+  uint32_t start;
+  uint32_t depth;
+} sg_depth_run;
+int sg_depth_begin(sg_ctx* ctx, const uint64_t* contig_len, uint32_t n_contigs);
+int sg_depth_add(sg_ctx* ctx, uint64_t* m_bases);
+int sg_depth_add_spans(sg_ctx* ctx, const uint32_t* contig, const uint64_t* start, const uint64_t* end, uint64_t n);
+int sg_depth_bins(sg_ctx* ctx, uint32_t contig, uint64_t bin, uint64_t* sums, uint64_t cap, uint64_t* n);
+int sg_depth_runs(sg_ctx* ctx, uint32_t contig, sg_depth_run* rows, uint64_t cap, uint64_t* n);
+int sg_depth_fetch(sg_ctx* ctx, uint32_t contig, uint64_t first, uint64_t n, uint32_t* depth);
+int sg_depth_reset(sg_ctx* ctx);
+int sg_depth_info(sg_ctx* ctx, uint32_t* n_contigs, uint64_t* m_bases, uint32_t* tile);
+int sg_depth_end(sg_ctx* ctx);
+
 /* When enabled, HIP events bracket every kernel of sg_sample on the ctx's stream;
  * sg_kernel_times() then returns the last pass's per-kernel milliseconds (after sg_result).     */
 int sg_set_profiling(sg_ctx* ctx, int enable);

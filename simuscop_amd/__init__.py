@@ -32,6 +32,8 @@ ENGINE_SYMBOLS = [
     "sg_bgzf_members", "sg_inflate_bgzf", "sg_train_bam_start", "sg_train_feed_bgzf", "sg_train_bam_info",
     "sg_release_cached_memory",
     "sg_truth_align", "sg_truth_map", "sg_truth_pieces", "sg_truth_reads", "sg_truth_bam", "sg_fetch_truth", "sg_truth_info",
+    "sg_depth_begin", "sg_depth_add", "sg_depth_add_spans", "sg_depth_bins", "sg_depth_runs", "sg_depth_fetch", "sg_depth_reset",
+    "sg_depth_info", "sg_depth_end",
 ]
 
 
@@ -105,6 +107,11 @@ class SgTruthRead(C.Structure):
                 ("tmpl_off", C.c_uint64), ("n_events", C.c_uint32), ("inside", C.c_uint32), ("events", C.c_uint32 * 32)]
 
 
+class SgDepthRun(C.Structure):
+    """sg_depth_run: a run of equal depth starts at `start` (sg_depth_runs)"""
+    _fields_ = [("start", C.c_uint32), ("depth", C.c_uint32)]
+
+
 class SgHapPatch(C.Structure):
     _fields_ = [("dst", C.c_uint64), ("chain", C.c_uint32), ("base", C.c_uint32)]
 
@@ -114,7 +121,8 @@ class SimuOptions(C.Structure):
                 ("fetch", C.c_int32), ("quiet", C.c_int32), ("shard_rank", C.c_int32), ("shard_world", C.c_int32),
                 ("output_dir", C.c_char_p), ("repeat_sample", C.c_int32), ("host_haplotypes", C.c_int32), ("gzip", C.c_int32),
                 ("shard_contigs", C.c_int32), ("no_eof_block", C.c_int32), ("exchange", C.c_void_p), ("exchange_user", C.c_void_p),
-                ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32)]
+                ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32),
+                ("truth_depth", C.c_int32)]
 
 
 # simu_options.exchange: all-reduce(sum) of n doubles over the ranks, in place
@@ -137,7 +145,8 @@ class SimuStats(C.Structure):
                 ("emit_kernel", C.c_int32), ("emit_slow_rows_lds", C.c_int32), ("emit_lds_bytes", C.c_uint32),
                 ("emit_clean_cap", C.c_uint32),
                 ("truth_records", C.c_uint64), ("truth_unmapped", C.c_uint64), ("truth_bytes", C.c_uint64),
-                ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double)]
+                ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double),
+                ("depth_bases", C.c_uint64), ("depth_rows", C.c_uint64), ("t_depth", C.c_double)]
 
 
 _engine = None
@@ -229,6 +238,16 @@ def load_engine():
     lib.sg_truth_bam.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.sg_fetch_truth.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
     lib.sg_truth_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    lib.sg_depth_begin.argtypes = [vp, u64p, C.c_uint32]
+    lib.sg_depth_add.argtypes = [vp, u64p]
+    lib.sg_depth_add_spans.argtypes = [vp, u32p, u64p, u64p, C.c_uint64]
+    lib.sg_depth_bins.argtypes = [vp, C.c_uint32, C.c_uint64, u64p, C.c_uint64, u64p]
+    lib.sg_depth_runs.argtypes = [vp, C.c_uint32, C.POINTER(SgDepthRun), C.c_uint64, u64p]
+    lib.sg_depth_fetch.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
+    lib.sg_depth_reset.argtypes = [vp]
+    lib.sg_depth_info.argtypes = [vp, u32p, u64p, u32p]
+    lib.sg_depth_end.argtypes = [vp]
     _engine = lib
     return lib
 
@@ -264,6 +283,8 @@ def load_host():
     lib.simu_get_stats.restype = None
     lib.simu_batch_slots.argtypes = [vp]
     lib.simu_batch_slots.restype = C.c_uint64
+    lib.simu_depth_format.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.simu_depth_format.restype = C.c_uint64
     _host = lib
     return lib
 
@@ -357,6 +378,24 @@ def truth_align(pieces, tmpl_off: int, tmpl_len: int, reverse: bool, events=(), 
 def release_cached_memory() -> None:
     """Device blocks that finished contexts left with the process go back to the runtime (sg_release_cached_memory)."""
     load_engine().sg_release_cached_memory()
+
+
+def depth_format(name: str, ln: int, bin_width: int, data) -> bytes:
+    """simu_depth_format (host only, no GPU): one contig's rows of a --truth-depth bedGraph file.  `data`: (start, depth)
+    pairs for bin_width == 1, the bins' sums otherwise."""
+    lib = load_host()
+    n = len(data)
+    if bin_width == 1:
+        arr = (SgDepthRun * max(n, 1))(*[SgDepthRun(int(a), int(b)) for a, b in data])
+    else:
+        arr = (C.c_uint64 * max(n, 1))(*[int(v) for v in data])
+    rows = C.c_uint64()
+    need = lib.simu_depth_format(name.encode(), ln, bin_width, arr, n, None, 0, C.byref(rows))
+    if need == 2 ** 64 - 1:
+        raise SimuError("simu_depth_format: the data does not describe a contig of that length")
+    buf = C.create_string_buffer(max(int(need), 1))
+    lib.simu_depth_format(name.encode(), ln, bin_width, arr, n, buf, need, C.byref(rows))
+    return buf.raw[:need]
 
 
 class Session:
@@ -468,6 +507,68 @@ class Session:
         a, b = C.c_uint64(), C.c_uint64()
         self._sg(self.eng.sg_truth_info(self.ctx, C.byref(a), C.byref(b)), "sg_truth_info")
         return a.value, b.value
+
+    # ---- true coverage (sessions opened with truth_depth=BIN: the driver hands over the piece map and begins the depth
+    # with the reference's contigs at the first prepare_batch; depth_begin starts one over contigs of the caller's) ----
+    def depth_begin(self, contig_len) -> None:
+        arr = (C.c_uint64 * max(len(contig_len), 1))(*[int(v) for v in contig_len])
+        self._sg(self.eng.sg_depth_begin(self.ctx, arr, len(contig_len)), "sg_depth_begin")
+
+    def depth_add(self) -> int:
+        """Add the reads of the last pass (after result()); returns the M bases added."""
+        mb = C.c_uint64()
+        self._sg(self.eng.sg_depth_add(self.ctx, C.byref(mb)), "sg_depth_add")
+        return mb.value
+
+    def depth_add_spans(self, contig, start, end) -> None:
+        """Add spans [start, end) of contigs (numpy arrays or sequences of equal length)."""
+        import numpy as np
+        c = np.ascontiguousarray(contig, dtype=np.uint32)
+        a = np.ascontiguousarray(start, dtype=np.uint64)
+        b = np.ascontiguousarray(end, dtype=np.uint64)
+        if not (len(c) == len(a) == len(b)):
+            raise ValueError("depth_add_spans: contig, start and end differ in length")
+        self._sg(self.eng.sg_depth_add_spans(self.ctx, c.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             b.ctypes.data_as(C.POINTER(C.c_uint64)), len(c)), "sg_depth_add_spans")
+
+    def depth_bins(self, contig: int, bin_width: int):
+        """64-bit sums of the per-base depths of the contig's bins of bin_width bases (numpy uint64)."""
+        import numpy as np
+        n = C.c_uint64()
+        self._sg(self.eng.sg_depth_bins(self.ctx, contig, bin_width, None, 0, C.byref(n)), "sg_depth_bins")
+        out = np.zeros(n.value, dtype=np.uint64)
+        if n.value:
+            self._sg(self.eng.sg_depth_bins(self.ctx, contig, bin_width, out.ctypes.data_as(C.POINTER(C.c_uint64)), n.value, C.byref(n)), "sg_depth_bins")
+        return out
+
+    def depth_runs(self, contig: int):
+        """The contig's runs of equal depth: numpy uint32 [n, 2] of (start, depth)."""
+        import numpy as np
+        n = C.c_uint64()
+        self._sg(self.eng.sg_depth_runs(self.ctx, contig, None, 0, C.byref(n)), "sg_depth_runs")
+        out = np.zeros((n.value, 2), dtype=np.uint32)
+        if n.value:
+            self._sg(self.eng.sg_depth_runs(self.ctx, contig, C.cast(out.ctypes.data, C.POINTER(SgDepthRun)), n.value, C.byref(n)), "sg_depth_runs")
+        return out
+
+    def depth_fetch(self, contig: int, first: int, n: int):
+        """Per-base depths of bases [first, first + n) (numpy uint32)."""
+        import numpy as np
+        out = np.zeros(n, dtype=np.uint32)
+        self._sg(self.eng.sg_depth_fetch(self.ctx, contig, first, n, out.ctypes.data_as(C.POINTER(C.c_uint32))), "sg_depth_fetch")
+        return out
+
+    def depth_reset(self) -> None:
+        self._sg(self.eng.sg_depth_reset(self.ctx), "sg_depth_reset")
+
+    def depth_info(self):
+        """(contigs, M bases added, bases per tile of the finishing pass)."""
+        nc, mb, tile = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        self._sg(self.eng.sg_depth_info(self.ctx, C.byref(nc), C.byref(mb), C.byref(tile)), "sg_depth_info")
+        return nc.value, mb.value, tile.value
+
+    def depth_end(self) -> None:
+        self._sg(self.eng.sg_depth_end(self.ctx), "sg_depth_end")
 
     def emit_info(self):
         """(items handed to the generic item code, whether the batch was re-emitted) of the last pass."""

@@ -2,6 +2,7 @@
 // Same positional argument, usage text and exit codes; optional flags are additive:
 //   --seed N  --device D  --out DIR  --no-write [--fetch]  --quiet  --rank R --world W  --stats  --host-haplotypes  --gzip
 //   --truth-bam   every read's true alignment as <stem>.truth.bam beside the FASTQ files (simulate.h)
+//   --truth-depth BIN   the reads' true coverage as <stem>.truth.depth.bedgraph (BIN 1: runs of equal depth; BIN > 1: means)
 //   --gpus N [--shard-contigs]
 //   --crlf-as-lf  --strict-bases  --unique-contigs   (each turns one kept reference quirk off: simulate.h)
 #include <dirent.h>
@@ -227,6 +228,16 @@ int main(int argc, char* argv[]) {
     else if (a == "--host-haplotypes") opt.host_haplotypes = 1;
     else if (a == "--gzip") opt.gzip = 1;
     else if (a == "--truth-bam") opt.truth_bam = 1;
+    else if (a == "--truth-depth") {
+      const char* v = val();
+      char* end = nullptr;
+      const long long bin = strtoll(v, &end, 10);
+      if (end == v || *end || bin < 1 || bin > 0x7FFFFFFFll) {
+        std::cerr << "Error: --truth-depth needs a bin width: an integer of at least 1 (got '" << v << "')" << std::endl;
+        return 1;
+      }
+      opt.truth_depth = (int32_t)bin;
+    }
     else if (a == "--shard-contigs") opt.shard_contigs = 1;
     else if (a == "--no-eof-block") opt.no_eof_block = 1;
     else if (a == "--crlf-as-lf") opt.crlf_as_lf = 1;
@@ -246,6 +257,11 @@ int main(int argc, char* argv[]) {
       usage(argv[0]);
       return 1;
     }
+  }
+  if (opt.truth_depth && (gpus > 1 || opt.shard_world > 1)) {
+    std::cerr << "Error: --truth-depth cannot be combined with --world or --gpus above 1: the ranks' partial depths would have to be "
+                 "summed, not concatenated" << std::endl;
+    return 1;
   }
   if (gpus > 1) {
     for (int i = 1; i < argc; i++) {
@@ -276,7 +292,8 @@ int main(int argc, char* argv[]) {
     fprintf(stderr,
             "stats: reads=%llu fragments=%llu bytes=%llu windows=%llu segments=%llu batches=%llu | load %.3fs (engine %.3fs reference %.3fs) haplotypes %.3fs "
             "plan %.3fs sample %.3fs (haplotype calls %.3fs sg_plan %.3fs) fetch %.3fs write %.3fs total %.3fs | kernels ms: plan %.3f namebase %.3f indel %.3f scan %.3f emit %.3f emit_slow %.3f | queued_items=%llu requeued_batches=%llu emit_kernel=%d slow_rows_lds=%d emit_lds=%u clean_cap=%u | compress %.3fs gz_bytes=%llu | "
-            "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f\n",
+            "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f | "
+            "depth_bases=%llu depth_rows=%llu depth_s=%.3f\n",
             (unsigned long long)st.reads, (unsigned long long)st.fragments, (unsigned long long)st.fastq_bytes,
             (unsigned long long)st.windows, (unsigned long long)st.segments, (unsigned long long)st.batches, st.t_load,
             st.t_engine, st.t_reference,
@@ -284,6 +301,7 @@ int main(int argc, char* argv[]) {
             st.kernel_ms[2], st.kernel_ms[3], st.kernel_ms[4], st.kernel_ms[5], (unsigned long long)st.queued_items,
             (unsigned long long)st.requeued_batches, st.emit_kernel, st.emit_slow_rows_lds, st.emit_lds_bytes,
             st.emit_clean_cap, st.t_compress, (unsigned long long)st.gz_bytes, (unsigned long long)st.truth_records,
-            (unsigned long long)st.truth_unmapped, (unsigned long long)st.truth_bytes, (unsigned long long)st.truth_bgzf_bytes, st.t_truth);
+            (unsigned long long)st.truth_unmapped, (unsigned long long)st.truth_bytes, (unsigned long long)st.truth_bgzf_bytes, st.t_truth,
+            (unsigned long long)st.depth_bases, (unsigned long long)st.depth_rows, st.t_depth);
   return 0;
 }

@@ -41,6 +41,41 @@ namespace {
 using Clock = std::chrono::steady_clock;
 inline double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
+// One contig's bedGraph rows appended to `out` (simu_depth_format, simulate.h); returns the lines, or UINT64_MAX for data
+// that does not describe a contig of `ln` bases.
+uint64_t depth_format(std::string& out, const std::string& name, uint64_t ln, uint64_t bin, const uint64_t* sums, const sg_depth_run* runs,
+                      uint64_t n) {
+  char buf[96];
+  uint64_t rows = 0;
+  if (bin == 1) {
+    if ((ln == 0) != (n == 0) || (n && runs[0].start != 0)) return UINT64_MAX;
+    for (uint64_t i = 0; i < n;) {
+      uint64_t j = i + 1;
+      while (j < n && runs[j].depth == runs[i].depth) j++;   // (the device's runs differ from their neighbours already)
+      for (uint64_t k = i + 1; k <= j && k < n; k++)
+        if (runs[k].start <= runs[k - 1].start || runs[k].start >= ln) return UINT64_MAX;
+      const uint64_t end = j < n ? runs[j].start : ln;
+      const int m = snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\n", (unsigned long long)runs[i].start, (unsigned long long)end,
+                             (unsigned long long)runs[i].depth);
+      out += name;
+      out.append(buf, (size_t)m);
+      rows++;
+      i = j;
+    }
+    return rows;
+  }
+  if (bin < 1 || n != (ln + bin - 1) / bin) return UINT64_MAX;
+  for (uint64_t k = 0; k < n; k++) {
+    const uint64_t a = k * bin, b = std::min(ln, a + bin);
+    const int m = snprintf(buf, sizeof buf, "\t%llu\t%llu\t%.4f\n", (unsigned long long)a, (unsigned long long)b,
+                           (double)sums[k] / (double)(b - a));
+    out += name;
+    out.append(buf, (size_t)m);
+    rows++;
+  }
+  return rows;
+}
+
 struct Engine {  // RAII around sg_ctx, turns status codes into simu::Error
   sg_ctx* ctx = nullptr;
   ~Engine() { if (ctx) sg_destroy(ctx); }
@@ -115,6 +150,7 @@ struct Driver {
   ~Driver() {
     if (pending.active && pending.th.joinable()) pending.th.join();
     if (pending.active && pending.handle && eng.ctx) sg_release_outputs(eng.ctx, pending.handle);
+    if (fd) fclose(fd);
     for (void* b : pinned)
       if (b && eng.ctx) sg_host_free(eng.ctx, b);
   }
@@ -193,6 +229,69 @@ struct Driver {
     }
     st.t_truth += since(t0);
   }
+  // ---- --truth-depth ----
+  // The depth array lives on the device from the first stem on; every piece adds its reads (depth_piece), a stem's file
+  // is made when the stem closes -- the device's runs or bin sums, contig by contig in the order of truth_refs(), put
+  // into text here (depth_format) -- and the array is zeroed for the next stem.
+  bool depth_begun = false, depth_stem = false;
+  FILE* fd = nullptr;   // <stem>.truth.depth.bedgraph
+  void depth_begin() {
+    if (!opt.truth_depth || depth_begun) return;
+    std::vector<uint64_t> len;
+    for (const auto& r : truth_refs()) len.push_back(r.second);
+    eng.check(sg_depth_begin(eng.ctx, len.data(), (uint32_t)len.size()), "sg_depth_begin");
+    depth_begun = true;
+  }
+  void depth_open(const std::string& dir, const std::string& stem) {
+    if (!opt.truth_depth) return;
+    auto t0 = Clock::now();
+    depth_begin();
+    depth_stem = true;
+    if (opt.write_files) {
+      const std::string a = dir + "/" + stem + ".truth.depth.bedgraph";
+      fd = fopen(a.c_str(), "wb");
+      if (!fd) throw Error("Error: can not open bedGraph file to save the true depth:\n" + a, -1);
+    }
+    st.t_depth += since(t0);
+  }
+  void depth_piece() {
+    auto t0 = Clock::now();
+    uint64_t mb = 0;
+    eng.check(sg_depth_add(eng.ctx, &mb), "sg_depth_add");
+    st.depth_bases += mb;
+    st.t_depth += since(t0);
+  }
+  void depth_close() {
+    if (!depth_stem) return;
+    auto t0 = Clock::now();
+    depth_stem = false;
+    struct Closer { FILE*& f; ~Closer() { if (f) fclose(f); f = nullptr; } } closer{fd};
+    const auto refs = truth_refs();
+    const uint64_t bin = (uint64_t)opt.truth_depth;
+    std::vector<uint64_t> sums;
+    std::vector<sg_depth_run> runs;
+    std::string text;
+    for (size_t c = 0; c < refs.size(); c++) {
+      uint64_t n = 0;
+      text.clear();
+      if (bin == 1) {
+        eng.check(sg_depth_runs(eng.ctx, (uint32_t)c, nullptr, 0, &n), "sg_depth_runs");
+        if (runs.size() < n) runs.resize(n);
+        if (n) eng.check(sg_depth_runs(eng.ctx, (uint32_t)c, runs.data(), n, &n), "sg_depth_runs");
+        st.depth_rows += depth_format(text, refs[c].first, refs[c].second, 1, nullptr, runs.data(), n);
+      } else {
+        eng.check(sg_depth_bins(eng.ctx, (uint32_t)c, bin, nullptr, 0, &n), "sg_depth_bins");
+        if (sums.size() < n) sums.resize(n);
+        if (n) eng.check(sg_depth_bins(eng.ctx, (uint32_t)c, bin, sums.data(), n, &n), "sg_depth_bins");
+        st.depth_rows += depth_format(text, refs[c].first, refs[c].second, bin, sums.data(), nullptr, n);
+      }
+      if (fd && !text.empty() && fwrite(text.data(), 1, text.size(), fd) != text.size())
+        throw Error("Error: short write to the true depth's bedGraph file", -1);
+    }
+    eng.check(sg_depth_reset(eng.ctx), "sg_depth_reset");
+    st.t_depth += since(t0);
+  }
+
   void open_sink(const std::string& dir, const std::string& stem, bool paired, const std::string& suffix) {
     sink.open(dir, stem, paired, suffix, opt.gzip != 0);
     if (!opt.truth_bam) return;
@@ -211,7 +310,7 @@ struct Driver {
                                     plan.pieces.size(), plan.literals.data(), plan.literals.size(), plan.patches.data(),
                                     plan.patches.size()),
                 "sg_build_haplotypes");
-      if (opt.truth_bam) {  // the copy list is the reads' way back to the reference: contig rows -> refIDs of the BAM header
+      if (opt.truth_bam || opt.truth_depth) {  // the copy list is the reads' way back to the reference: contig rows -> refIDs of the BAM header
         const std::vector<int32_t> ref_ids = truth_ref_ids();
         eng.check(sg_truth_map(eng.ctx, plan.pieces.data(), plan.piece_seg_first.data(), plan.piece_seg_first.size(), ref_ids.data(), (uint32_t)ref_ids.size()),
                   "sg_truth_map");
@@ -571,6 +670,7 @@ struct Driver {
   // the whole shard as one engine batch (step-by-step sessions: bench.py keeps it resident)
   bool prepare_batch(const std::string& popu, const std::string& chr) {
     if (!build_batch(popu, chr)) return false;
+    depth_begin();   // (a session has no stems: its caller adds, reads and resets the depth itself)
     plan_range(cur.a0, cur.a1);
     return true;
   }
@@ -628,6 +728,7 @@ struct Driver {
     st.reads += paired ? 2 * nf : nf;
     st.fastq_bytes += n1 + n2;
     if (opt.truth_bam) truth_piece(sink);
+    if (opt.truth_depth) depth_piece();
     if (!(opt.write_files || opt.fetch)) return;
     bool compressed = false;
     if (opt.gzip) {
@@ -758,6 +859,13 @@ struct Driver {
     if (opt.truth_bam && opt.host_haplotypes)
       throw Error("Error: --truth-bam needs the haplotypes assembled on the device (their copy lists map the reads back to the "
                   "reference); it cannot be combined with --host-haplotypes");
+    if (opt.truth_depth < 0) throw Error("Error: --truth-depth needs a bin width of at least 1");
+    if (opt.truth_depth && opt.host_haplotypes)
+      throw Error("Error: --truth-depth needs the haplotypes assembled on the device (their copy lists map the reads back to the "
+                  "reference); it cannot be combined with --host-haplotypes");
+    if (opt.truth_depth && opt.shard_world > 1)
+      throw Error("Error: --truth-depth cannot be combined with --world or --gpus above 1: the ranks' partial depths would have to "
+                  "be summed, not concatenated");
     cfg.load(config_path);
     seed = opt.has_seed ? opt.seed : (uint64_t)cfg.num["seed"];
     const int device = opt.device >= 0 ? opt.device : (int)cfg.num["device"];
@@ -828,6 +936,7 @@ struct Driver {
     sink.truth_eof_block = !opt.no_eof_block && (opt.shard_world <= 1 || opt.shard_rank == opt.shard_world - 1);
     if (genome.mix_props.empty()) {
       if (opt.write_files) open_sink(out_dir, popus[0], paired, suffix);
+      depth_open(out_dir, popus[0]);
       set_read_counts(popus[0], reads);
       for (const std::string& chr : genome.chromosomes) run_batch(popus[0], chr, sink);
     } else {
@@ -841,7 +950,9 @@ struct Driver {
           stem += buf;
         }
         drain_wait();  // the previous mixture's last batch still writes into the files about to be closed
+        depth_close();
         if (opt.write_files) open_sink(out_dir, stem, paired, suffix);
+        depth_open(out_dir, stem);
         for (size_t i = 0; i < popus.size(); i++) {
           const long popu_reads = (long)(reads * props[i] * acn[popus[i]] / w_acn);  // long*float is a float product (Genome.cpp:935)
           set_read_counts(popus[i], popu_reads);
@@ -850,6 +961,7 @@ struct Driver {
       }
     }
     drain_wait();
+    depth_close();
     sink.close();
     log("\nReads generation done!\n");
     st.t_total = since(t_all);
@@ -864,6 +976,18 @@ extern "C" void simu_default_options(simu_options* o) {
   o->device = -1;
   o->write_files = 1;
   o->shard_world = 1;
+}
+
+extern "C" uint64_t simu_depth_format(const char* name, uint64_t ln, uint64_t bin, const void* data, uint64_t n, char* out, uint64_t cap,
+                                      uint64_t* rows) {
+  if (!name || (n && !data) || bin < 1) return UINT64_MAX;
+  std::string text;
+  const uint64_t r = simu::depth_format(text, name, ln, bin, bin == 1 ? nullptr : (const uint64_t*)data,
+                                        bin == 1 ? (const sg_depth_run*)data : nullptr, n);
+  if (r == UINT64_MAX) return UINT64_MAX;
+  if (rows) *rows = r;
+  if (out && text.size() <= cap) memcpy(out, text.data(), text.size());
+  return text.size();
 }
 
 extern "C" void simu_assign_contigs(const uint64_t* lengths, int32_t n, int32_t world, int32_t* owner_out) {

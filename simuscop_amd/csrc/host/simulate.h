@@ -43,6 +43,11 @@ typedef struct simu_options {
                            //    records are made and compressed on the device, piece by piece, in FASTQ order); needs the
                            //    device-assembled haplotypes (refused with host_haplotypes).  Sharded runs write parts like the
                            //    FASTQ parts: rank 0's carries the header, the last rank's the BGZF end-of-file block
+  int32_t truth_depth;     // BIN >= 1: write the reads' true coverage to <stem>.truth.depth.bedgraph beside the FASTQ files
+                           //    (sg_depth_*: every M base of every read's true alignment, summed over the pieces, chromosomes
+                           //    and populations written into the stem); BIN 1: one row per run of equal depth, BIN > 1: the
+                           //    mean depth of every BIN bases.  0: off.  Needs the device-assembled haplotypes like truth_bam;
+                           //    refused in a sharded run (partial depths would have to be summed)
 } simu_options;
 
 typedef struct simu_stats {
@@ -75,6 +80,9 @@ typedef struct simu_stats {
   uint64_t truth_bytes;    // ... bytes of the record stream and of its BGZF members (header and end-of-file block aside)
   uint64_t truth_bgzf_bytes;
   double t_truth;          // sg_truth_bam calls + fetching and writing their members (synchronous, per piece)
+  uint64_t depth_bases;    // truth_depth: M bases added to the depth, ...
+  uint64_t depth_rows;     // ... bedGraph lines made (written unless write_files == 0)
+  double t_depth;          // sg_depth_* calls, formatting and writing the rows
 } simu_stats;
 
 // Returns 0 on success.  On failure returns the exit code the reference would use and writes the
@@ -92,6 +100,15 @@ void simu_assign_contigs(const uint64_t* lengths, int32_t n, int32_t world, int3
 // handed to sg_build_haplotypes (Genome::segment_pieces), materialised on the host -- and compared byte for byte.
 // Returns 0 when all chains agree; otherwise 1 and a description in `err`.
 int simu_selftest_haplotypes(const char* config_path, uint64_t seed, char* err, size_t err_len);
+
+// One contig's rows of a --truth-depth bedGraph file ("name<TAB>start<TAB>end<TAB>value\n", 0-based, half open, tiling
+// [0, ln)), host only.  bin == 1: `data` is n sg_depth_run rows {uint32 start, uint32 depth}, the first at 0, starts
+// ascending; a row reaches to the next one's start (the last to ln), the value is the depth as a decimal integer, and
+// neighbours of equal depth come out as one row.  bin > 1: `data` is n = ceil(ln / bin) uint64 sums; one row per bin,
+// unmerged, the value printf("%.4f", (double)sum / (double)width) with the row's own width.  The text is written to
+// out[0 .. cap) when it fits; returns its length (call again with that much room), *rows = lines.  UINT64_MAX: `data`
+// does not describe a contig of ln bases.
+uint64_t simu_depth_format(const char* name, uint64_t ln, uint64_t bin, const void* data, uint64_t n, char* out, uint64_t cap, uint64_t* rows);
 
 // ---- step-by-step session (bench.py / multi-GPU launcher) ----
 typedef struct simu_session simu_session;

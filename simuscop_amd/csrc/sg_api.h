@@ -1,5 +1,6 @@
-// sg_api.h -- what the two files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
-// sink, reference, haplotypes, window planner) and sg_api_train.cpp (profile training, BGZF / BAM input).  Internal: the
+// sg_api.h -- what the files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
+// sink, reference, haplotypes, window planner), sg_api_train.cpp (profile training, BGZF / BAM input) and
+// sg_api_depth.cpp (true coverage).  Internal: the
 // ABI itself is include/simuscop_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,6 +73,17 @@ struct sg_ctx {
     uint64_t rec_bytes = 0, gz_bytes = 0, records = 0, unmapped = 0;
   } truth;
   DevBuf truth_map, truth_work, truth_rec, truth_gz, truth_rows;
+  // true coverage (sg_depth_*, sg_api_depth.cpp): the contigs' lengths and first slots in depth_diff, the flat int32
+  // difference array (depth_meta holds both tables for the kernels); depth_work holds one contig's tile sums, run-start
+  // counts and their scans (`scanned` says whose, until the array changes), depth_out a call's bins, rows or depths and
+  // the spans of sg_depth_add_spans.  Without sg_depth_begin nothing is kept and nothing is allocated.
+  struct Depth {
+    bool on = false;
+    std::vector<uint64_t> len, off;
+    uint64_t slots = 0, m_bases = 0, scanned_starts = 0;
+    int64_t scanned = -1;
+  } depth;
+  DevBuf depth_diff, depth_meta, depth_work, depth_out;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // device-made sampling plan: window weights per store id (sg_windows_build), the batch table of sg_plan_windows
   std::map<uint32_t, DevBuf> wstore;

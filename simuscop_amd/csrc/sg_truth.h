@@ -155,6 +155,35 @@ __host__ __device__ inline uint32_t truth_reg2bin(int64_t beg, int64_t end) {
   return 0;
 }
 
+// What the pass left of read (t, m): the meta row of indel_kernel and the fragment's window
+struct ReadGeom {
+  bool live, inside;      // inside: the template lies in its chain
+  uint32_t chain, reverse, np, nev, hdr;
+  uint64_t tmpl_off;      // chain-local
+  const uint32_t* events;
+};
+__device__ __forceinline__ ReadGeom read_geom(const DevProfile& P, const DevBatch& B, uint32_t t, uint32_t m) {
+  ReadGeom g = {};
+  const size_t idx = (size_t)m * B.n_slots + t;
+  const uint4 m1 = B.meta[idx * 3 + 1];
+  const uint32_t flen = m1.x & 0x3FFFFFFFu;
+  g.live = flen != 0u;
+  if (!g.live) return g;
+  const uint4 m0 = B.meta[idx * 3];
+  const uint64_t foff = ((uint64_t)m0.y << 32) | m0.x;
+  const uint32_t L = (uint32_t)P.L;
+  g.reverse = m1.x >> 31;
+  g.np = m1.y & 0xFFFFu;
+  g.nev = (m1.y >> 16) & 63u;   // the row's count: indel_kernel drops the events of a read that would get shorter than 50
+  g.hdr = m1.y >> 22;
+  g.chain = B.windows[B.pairs[t].win].chain;
+  const uint64_t c0 = B.chain_off[g.chain], tmpl = g.reverse ? foff + flen - L : foff;
+  g.inside = flen >= L && tmpl >= c0 && tmpl - c0 + L <= B.chain_len[g.chain];
+  g.tmpl_off = tmpl - c0;
+  g.events = B.events + idx * SG_MAX_EVENTS;
+  return g;
+}
+
 constexpr uint32_t kTruthMaxOps = 256;     // CIGAR operations of one record (more: SG_ERR_OVERFLOW)
 constexpr uint32_t kTruthWaveOps = 2048;   // ... and of the 64 records one wave packs
 
@@ -189,5 +218,37 @@ struct TruthReadRow {
   uint32_t events[SG_MAX_EVENTS];
 };
 void launch_truth_reads(const DevProfile& P, const DevBatch& B, uint32_t mate, uint32_t first_slot, uint32_t n, TruthReadRow* out, hipStream_t s);
+
+// ---- true coverage (simuReads --truth-depth; kernels: sg_depth.hip) ----
+// One flat int32 difference array: contig c owns slots [off[c], off[c] + len[c] + 1), off[c] a multiple of 4 (16-byte
+// loads).  A run [a, b) of M bases adds +1 at a and -1 at b; the depth of base i is the sum of slots 0..i, taken modulo
+// 2^32 (so a depth of up to 2^32 - 1 comes out right).
+constexpr uint32_t kDepthStageRuns = 8; // M runs of a read depth_add_kernel stages in LDS (a read with more walks twice)
+constexpr uint32_t kDepthTile = 4096;   // bases one wave of the finishing pass rebuilds (16 steps of 64 lanes x 4 bases)
+struct DepthJob {
+  const TruthPiece* pieces;
+  const uint64_t* chain_first;
+  uint32_t n_chains, n_reads;
+  int32_t* diff;
+  const uint64_t* contig_off;    // [n_contigs] first slot of each contig
+  const uint64_t* contig_len;    // [n_contigs]
+  uint32_t n_contigs;
+  uint32_t stage_runs;           // <= kDepthStageRuns
+  unsigned long long* counters;  // [0] M bases, [1] flags: 1 a run outside its contig (not written), 2 a walk whose runs do not end at its `end`
+};
+struct DepthRun { uint32_t start, depth; };   // sg_depth_run
+// one contig's slots for the finishing pass
+struct DepthView {
+  const int32_t* diff;   // 16-byte aligned
+  uint32_t len, n_tiles;
+};
+void launch_depth_add(const DevProfile& P, const DevBatch& B, const DepthJob& J, hipStream_t s);
+void launch_depth_spans(const DepthJob& J, const uint32_t* contig, const uint64_t* start, const uint64_t* end, uint64_t n, hipStream_t s);
+// per tile: the sum of its differences and the number of its run starts (base 0, and every base whose difference is not 0)
+void launch_depth_tiles(const DepthView& V, uint32_t* tile_sum, uint32_t* tile_starts, hipStream_t s);
+// tile_base: the exclusive scan of tile_sum (its low 32 bits are the depth in front of the tile)
+void launch_depth_bins(const DepthView& V, const uint64_t* tile_base, uint32_t bin, unsigned long long* sums, hipStream_t s);
+void launch_depth_runs(const DepthView& V, const uint64_t* tile_base, const uint64_t* start_base, DepthRun* rows, uint64_t cap, hipStream_t s);
+void launch_depth_fetch(const DepthView& V, const uint64_t* tile_base, uint32_t first, uint32_t n, uint32_t* out, hipStream_t s);
 
 }  // namespace sg

@@ -33,35 +33,6 @@ __device__ __forceinline__ uint64_t text_offset(const DevBatch& B, uint32_t m, u
          B.recloc[(size_t)m * B.n_slots + t];
 }
 
-// What the pass left of read (t, m): the meta row of indel_kernel and the fragment's window
-struct ReadGeom {
-  bool live, inside;      // inside: the template lies in its chain
-  uint32_t chain, reverse, np, nev, hdr;
-  uint64_t tmpl_off;      // chain-local
-  const uint32_t* events;
-};
-__device__ __forceinline__ ReadGeom read_geom(const DevProfile& P, const DevBatch& B, uint32_t t, uint32_t m) {
-  ReadGeom g = {};
-  const size_t idx = (size_t)m * B.n_slots + t;
-  const uint4 m1 = B.meta[idx * 3 + 1];
-  const uint32_t flen = m1.x & 0x3FFFFFFFu;
-  g.live = flen != 0u;
-  if (!g.live) return g;
-  const uint4 m0 = B.meta[idx * 3];
-  const uint64_t foff = ((uint64_t)m0.y << 32) | m0.x;
-  const uint32_t L = (uint32_t)P.L;
-  g.reverse = m1.x >> 31;
-  g.np = m1.y & 0xFFFFu;
-  g.nev = (m1.y >> 16) & 63u;   // the row's count: indel_kernel drops the events of a read that would get shorter than 50
-  g.hdr = m1.y >> 22;
-  g.chain = B.windows[B.pairs[t].win].chain;
-  const uint64_t c0 = B.chain_off[g.chain], tmpl = g.reverse ? foff + flen - L : foff;
-  g.inside = flen >= L && tmpl >= c0 && tmpl - c0 + L <= B.chain_len[g.chain];
-  g.tmpl_off = tmpl - c0;
-  g.events = B.events + idx * SG_MAX_EVENTS;
-  return g;
-}
-
 __device__ __forceinline__ uint32_t qname_len(const DevBatch& B, uint32_t hdr) { return hdr - 2u - (B.paired ? 2u : 0u); }
 
 __global__ __launch_bounds__(256) void truth_size_kernel(DevProfile P, DevBatch B, TruthJob J) {
