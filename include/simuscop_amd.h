@@ -415,6 +415,52 @@ int sg_depth_reset(sg_ctx* ctx);
 int sg_depth_info(sg_ctx* ctx, uint32_t* n_contigs, uint64_t* m_bases, uint32_t* tile);
 int sg_depth_end(sg_ctx* ctx);
 
+/* ---- true allele counts: per variant, the reads that cover the site and those that carry the allele
+ * (simuReads --truth-variants) ----
+ * A read counts by the haplotype bases its template was cut from (its read-length chain bases; sequencing errors,
+ * strand and mate play no part), both mates of a pair as reads.  Label every template base by its piece (the map of
+ * sg_truth_map): R(c, x) in a reference piece, Lit in a literal one.  A row (contig c, position p, 0-based):
+ *   kind 0, SNV, allele a      every base R(c, p): total; alt when the chain's base code there is a's
+ *   kind 1, insertion, len k   every base R(c, p) with a template base behind it: total when that is R(c, p + 1); total
+ *                              and alt when it is the first base of a literal piece of exactly k bases that lies inside
+ *                              the template and has a template base behind it
+ *   kind 2, deletion, len k    (bases [p, p + k), p >= 1) every base R(c, p - 1) with a template base behind it: total
+ *                              when that is R(c, p); total and alt when it is R(c, p + k)
+ * Counts are per occurrence, uint32, modulo 2^32, and add up over passes.  Additive: a context that never calls
+ * sg_variants_begin launches no kernel of this part and holds no device memory for it; every call below before
+ * sg_variants_begin is SG_ERR_INVALID.
+ *   sg_variants_begin   rows sorted by (contig, pos, kind, allele, len), no two alike; kind 0: allele an ASCII letter,
+ *                       len 0; kinds 1, 2: len >= 1, allele 0; pos < 2^32; anything else: SG_ERR_INVALID.  Uploads the
+ *                       table and zeroes the counters; a second call replaces the state
+ *   sg_variants_add     after sg_result and sg_truth_map: counts the current pass's reads; *reads_hit = reads with at
+ *                       least one count, *hits = counts of total.  Refuses a pass that ran under SG_DIAG and a context
+ *                       without a piece map, like sg_depth_add
+ *   sg_variants_counts  out[i] = {alt, total} of row i; *n = rows; cap == 0 gives the count alone; SG_ERR_OVERFLOW when
+ *                       0 < cap < *n
+ *   sg_variants_reset   zeroes the counters, keeps the buffers
+ *   sg_variants_info    rows, and reads_hit / hits summed since sg_variants_begin / sg_variants_reset
+ *   sg_variants_end     frees everything
+ *   sg_variant_observe  host only, no context: the same rule for one template.  `pieces` are the chain's pieces in
+ *                       offset order, the template tmpl_len bases from tmpl_off on, codes[i] the chain's base code
+ *                       (sg_haplotype_codes form: A0 C1 T2 G3) of template base i; rows as for sg_variants_begin.  One
+ *                       (hit_row, hit_alt) entry per count of total, in walk order; *n_hits = their number (all are
+ *                       counted, the first cap are written)                                                          */
+typedef struct sg_variant {
+  uint32_t contig;   /* BAM refID */
+  uint32_t kind;     /* 0 SNV, 1 insertion, 2 deletion */
+  uint64_t pos;      /* 0-based */
+  uint32_t len;
+  uint32_t allele;
+} sg_variant;
+int sg_variants_begin(sg_ctx* ctx, const sg_variant* rows, uint64_t n);
+int sg_variants_add(sg_ctx* ctx, uint64_t* reads_hit, uint64_t* hits);
+int sg_variants_counts(sg_ctx* ctx, uint32_t* out, uint64_t cap, uint64_t* n);
+int sg_variants_reset(sg_ctx* ctx);
+int sg_variants_info(sg_ctx* ctx, uint64_t* n_rows, uint64_t* reads_hit, uint64_t* hits);
+int sg_variants_end(sg_ctx* ctx);
+int sg_variant_observe(const sg_truth_piece* pieces, uint64_t n_pieces, const uint8_t* codes, uint64_t tmpl_off, uint32_t tmpl_len,
+                       const sg_variant* rows, uint64_t n_rows, uint32_t* hit_row, uint8_t* hit_alt, uint64_t cap, uint64_t* n_hits);
+
 /* When enabled, HIP events bracket every kernel of sg_sample on the ctx's stream;
  * sg_kernel_times() then returns the last pass's per-kernel milliseconds (after sg_result).     */
 int sg_set_profiling(sg_ctx* ctx, int enable);

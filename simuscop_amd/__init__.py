@@ -34,6 +34,8 @@ ENGINE_SYMBOLS = [
     "sg_truth_align", "sg_truth_map", "sg_truth_pieces", "sg_truth_reads", "sg_truth_bam", "sg_fetch_truth", "sg_truth_info",
     "sg_depth_begin", "sg_depth_add", "sg_depth_add_spans", "sg_depth_bins", "sg_depth_runs", "sg_depth_fetch", "sg_depth_reset",
     "sg_depth_info", "sg_depth_end",
+    "sg_variants_begin", "sg_variants_add", "sg_variants_counts", "sg_variants_reset", "sg_variants_info", "sg_variants_end",
+    "sg_variant_observe",
 ]
 
 
@@ -112,6 +114,11 @@ class SgDepthRun(C.Structure):
     _fields_ = [("start", C.c_uint32), ("depth", C.c_uint32)]
 
 
+class SgVariant(C.Structure):
+    """sg_variant: one row of the variant table (sg_variants_begin, sg_variant_observe)"""
+    _fields_ = [("contig", C.c_uint32), ("kind", C.c_uint32), ("pos", C.c_uint64), ("len", C.c_uint32), ("allele", C.c_uint32)]
+
+
 class SgHapPatch(C.Structure):
     _fields_ = [("dst", C.c_uint64), ("chain", C.c_uint32), ("base", C.c_uint32)]
 
@@ -122,7 +129,7 @@ class SimuOptions(C.Structure):
                 ("output_dir", C.c_char_p), ("repeat_sample", C.c_int32), ("host_haplotypes", C.c_int32), ("gzip", C.c_int32),
                 ("shard_contigs", C.c_int32), ("no_eof_block", C.c_int32), ("exchange", C.c_void_p), ("exchange_user", C.c_void_p),
                 ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32),
-                ("truth_depth", C.c_int32)]
+                ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
 
 
 # simu_options.exchange: all-reduce(sum) of n doubles over the ranks, in place
@@ -146,6 +153,7 @@ class SimuStats(C.Structure):
                 ("emit_clean_cap", C.c_uint32),
                 ("truth_records", C.c_uint64), ("truth_unmapped", C.c_uint64), ("truth_bytes", C.c_uint64),
                 ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double),
+                ("variant_rows", C.c_uint64), ("variant_dropped", C.c_uint64), ("variant_hits", C.c_uint64), ("t_variants", C.c_double),
                 ("depth_bases", C.c_uint64), ("depth_rows", C.c_uint64), ("t_depth", C.c_double)]
 
 
@@ -248,6 +256,15 @@ def load_engine():
     lib.sg_depth_reset.argtypes = [vp]
     lib.sg_depth_info.argtypes = [vp, u32p, u64p, u32p]
     lib.sg_depth_end.argtypes = [vp]
+    u8p = C.POINTER(C.c_uint8)
+    lib.sg_variants_begin.argtypes = [vp, C.POINTER(SgVariant), C.c_uint64]
+    lib.sg_variants_add.argtypes = [vp, u64p, u64p]
+    lib.sg_variants_counts.argtypes = [vp, u32p, C.c_uint64, u64p]
+    lib.sg_variants_reset.argtypes = [vp]
+    lib.sg_variants_info.argtypes = [vp, u64p, u64p, u64p]
+    lib.sg_variants_end.argtypes = [vp]
+    lib.sg_variant_observe.argtypes = [C.POINTER(SgTruthPiece), C.c_uint64, u8p, C.c_uint64, C.c_uint32, C.POINTER(SgVariant), C.c_uint64,
+                                       u32p, u8p, C.c_uint64, u64p]
     _engine = lib
     return lib
 
@@ -285,6 +302,12 @@ def load_host():
     lib.simu_batch_slots.restype = C.c_uint64
     lib.simu_depth_format.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.simu_depth_format.restype = C.c_uint64
+    cpp, u64p = C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)
+    lib.simu_variants_format.argtypes = [cpp, u64p, C.c_uint32, cpp, C.c_uint32, C.c_char_p, cpp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                         cpp, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64,
+                                         u64p, u64p]
+    lib.simu_variants_format.restype = C.c_uint64
+    lib.simu_variant_table.argtypes = [vp, C.c_void_p, C.c_uint64, u64p, C.c_char_p, C.c_size_t]
     _host = lib
     return lib
 
@@ -396,6 +419,72 @@ def depth_format(name: str, ln: int, bin_width: int, data) -> bytes:
     buf = C.create_string_buffer(max(int(need), 1))
     lib.simu_depth_format(name.encode(), ln, bin_width, arr, n, buf, need, C.byref(rows))
     return buf.raw[:need]
+
+
+def _variant_rows(rows):
+    """(contig, kind, pos, len, allele) tuples -> an SgVariant array; an allele may be a letter"""
+    arr = (SgVariant * max(len(rows), 1))()
+    for i, (contig, kind, pos, ln, allele) in enumerate(rows):
+        arr[i] = SgVariant(int(contig), int(kind), int(pos), int(ln), ord(allele) if isinstance(allele, str) else int(allele))
+    return arr
+
+
+def variant_observe(pieces, codes, tmpl_off: int, tmpl_len: int, rows, cap: int = 1024):
+    """sg_variant_observe (host only, no GPU): what one template counts.  `pieces`: (dst, src, len, contig, kind, seg_first)
+    of the chain in offset order; `codes`: the template's tmpl_len chain base codes (A0 C1 T2 G3); `rows`: the sorted
+    table as (contig, kind, pos, len, allele) tuples (pieces and rows may be ctypes arrays made before, codes a
+    contiguous numpy uint8 array).  Returns [(row index, is_alt)], one entry per count of total."""
+    lib = load_engine()
+    arr = pieces if isinstance(pieces, C.Array) else (SgTruthPiece * len(pieces))(*[SgTruthPiece(*p) for p in pieces])
+    if hasattr(codes, "ctypes"):   # a numpy uint8 array
+        cod = codes.ctypes.data_as(C.POINTER(C.c_uint8))
+    else:
+        cod = (C.c_uint8 * max(len(codes), 1))(*[int(c) for c in codes])
+    tab = rows if isinstance(rows, C.Array) else _variant_rows(rows)
+    n_rows = len(rows)
+    while True:
+        hr, ha, n = (C.c_uint32 * cap)(), (C.c_uint8 * cap)(), C.c_uint64()
+        rc = lib.sg_variant_observe(arr, len(pieces), cod, tmpl_off, tmpl_len, tab, n_rows, hr, ha, cap, C.byref(n))
+        if rc != 0:
+            raise SimuError(f"sg_variant_observe failed (code {rc})")
+        if n.value <= cap:
+            return [(hr[i], bool(ha[i])) for i in range(n.value)]
+        cap = n.value
+
+
+def variants_format(contigs, populations, rows, counts=None, want_table: bool = False):
+    """simu_variants_format (host only, no GPU): a --truth-variants file made from raw input rows.  `contigs`: (name,
+    length) in BAM refID order; `populations`: names in config order; `rows`: (kind, contig name, 1-based pos, population
+    index, text) with kind 's' / 'p' / 'i' / 'd' and text the alt base, the inserted sequence or the deletion length;
+    `counts`: (alt, total) per table row, or None for zeros.  Returns (text, table rows, dropped input rows), and with
+    want_table the table as (contig, kind, pos, len, allele) tuples as a fourth item."""
+    lib = load_host()
+    n_c, n_p, n = len(contigs), len(populations), len(rows)
+    cn = (C.c_char_p * max(n_c, 1))(*[c[0].encode() for c in contigs])
+    cl = (C.c_uint64 * max(n_c, 1))(*[int(c[1]) for c in contigs])
+    pn = (C.c_char_p * max(n_p, 1))(*[p.encode() for p in populations])
+    kind = b"".join(r[0].encode() for r in rows)
+    rc = (C.c_char_p * max(n, 1))(*[r[1].encode() for r in rows])
+    pos = (C.c_int64 * max(n, 1))(*[int(r[2]) for r in rows])
+    pop = (C.c_int32 * max(n, 1))(*[int(r[3]) for r in rows])
+    txt = (C.c_char_p * max(n, 1))(*[str(r[4]).encode() for r in rows])
+    n_rows, dropped = C.c_uint64(), C.c_uint64()
+    cnt, n_cnt = None, 0
+    if counts is not None:
+        flat = [int(v) for pair in counts for v in pair]
+        cnt, n_cnt = (C.c_uint32 * max(len(flat), 1))(*flat), len(counts)
+    call = lambda tab, cap_t, out, cap: lib.simu_variants_format(cn, cl, n_c, pn, n_p, kind, rc, pos, pop, txt, n, cnt, n_cnt, tab, cap_t, out, cap,
+                                                                 C.byref(n_rows), C.byref(dropped))
+    need = call(None, 0, None, 0)
+    if need == 2 ** 64 - 1:
+        raise SimuError(f"simu_variants_format: the counts do not fit the table of {n_rows.value} rows")
+    buf = C.create_string_buffer(max(int(need), 1))
+    tab = (SgVariant * max(n_rows.value, 1))()
+    call(C.cast(tab, C.c_void_p), n_rows.value, buf, need)
+    res = (buf.raw[:need], n_rows.value, dropped.value)
+    if want_table:
+        res += ([(v.contig, v.kind, v.pos, v.len, v.allele) for v in tab[:n_rows.value]],)
+    return res
 
 
 class Session:
@@ -569,6 +658,54 @@ class Session:
 
     def depth_end(self) -> None:
         self._sg(self.eng.sg_depth_end(self.ctx), "sg_depth_end")
+
+    # ---- true allele counts (sessions opened with truth_variants=1: the driver hands over the piece map and begins the
+    # counts with its own table at the first prepare_batch; variants_begin starts over with a table of the caller's) ----
+    def haplotype_codes(self, chain: int, offset: int, n: int):
+        """Base codes (A0 C1 T2 G3, N 4) of chain bases [offset, offset + n) on the device (numpy uint8)."""
+        import numpy as np
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self._sg(self.eng.sg_haplotype_codes(self.ctx, chain, offset, n, out.ctypes.data_as(C.c_char_p)), "sg_haplotype_codes")
+        return out[:n]
+
+    def variant_table(self):
+        """The driver's variant table for the open config: (contig, kind, pos, len, allele) tuples, allele an ASCII code."""
+        n = C.c_uint64()
+        self._check(self.lib.simu_variant_table(self._h, None, 0, C.byref(n), self._err, len(self._err)))
+        arr = (SgVariant * max(n.value, 1))()
+        self._check(self.lib.simu_variant_table(self._h, C.cast(arr, C.c_void_p), n.value, C.byref(n), self._err, len(self._err)))
+        return [(v.contig, v.kind, v.pos, v.len, v.allele) for v in arr[:n.value]]
+
+    def variants_begin(self, rows) -> None:
+        self._sg(self.eng.sg_variants_begin(self.ctx, _variant_rows(rows), len(rows)), "sg_variants_begin")
+
+    def variants_add(self):
+        """Count the reads of the last pass (after result()); returns (reads with a hit, hits)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._sg(self.eng.sg_variants_add(self.ctx, C.byref(a), C.byref(b)), "sg_variants_add")
+        return a.value, b.value
+
+    def variants_counts(self):
+        """numpy uint32 [rows, 2] of (alt, total)."""
+        import numpy as np
+        n = C.c_uint64()
+        self._sg(self.eng.sg_variants_counts(self.ctx, None, 0, C.byref(n)), "sg_variants_counts")
+        out = np.zeros((n.value, 2), dtype=np.uint32)
+        if n.value:
+            self._sg(self.eng.sg_variants_counts(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)), "sg_variants_counts")
+        return out
+
+    def variants_reset(self) -> None:
+        self._sg(self.eng.sg_variants_reset(self.ctx), "sg_variants_reset")
+
+    def variants_info(self):
+        """(rows, reads with a hit, hits) since variants_begin / variants_reset."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._sg(self.eng.sg_variants_info(self.ctx, C.byref(a), C.byref(b), C.byref(c)), "sg_variants_info")
+        return a.value, b.value, c.value
+
+    def variants_end(self) -> None:
+        self._sg(self.eng.sg_variants_end(self.ctx), "sg_variants_end")
 
     def emit_info(self):
         """(items handed to the generic item code, whether the batch was re-emitted) of the last pass."""

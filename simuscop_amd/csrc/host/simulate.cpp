@@ -25,6 +25,7 @@
 
 #include "../../../include/simuscop_amd.h"
 #include "genome.h"
+#include "truth_variants.h"
 
 namespace simu {
 
@@ -151,6 +152,7 @@ struct Driver {
     if (pending.active && pending.th.joinable()) pending.th.join();
     if (pending.active && pending.handle && eng.ctx) sg_release_outputs(eng.ctx, pending.handle);
     if (fd) fclose(fd);
+    if (fv) fclose(fv);
     for (void* b : pinned)
       if (b && eng.ctx) sg_host_free(eng.ctx, b);
   }
@@ -292,6 +294,100 @@ struct Driver {
     st.t_depth += since(t0);
   }
 
+  // ---- --truth-variants ----
+  // The table is built once from the variation and SNP rows of all populations (variants_build) and lives on the device
+  // with its two counters per row from the first stem on; every piece counts its reads (variants_piece), a stem's file
+  // is written when the stem closes and the counters are zeroed for the next stem.
+  VariantTable vtable;
+  bool variants_built = false, variants_begun = false, variants_stem = false;
+  FILE* fv = nullptr;   // <stem>.truth.variants.tsv
+  void variants_build() {
+    if (variants_built) return;
+    variants_built = true;
+    // contig key (the variant files' names) -> BAM refID, as truth_refs() numbers the contigs
+    std::vector<int32_t> id_of_row(genome.fa.contigs.size(), -1);
+    {
+      std::vector<char> named(genome.fa.contigs.size(), 0);
+      for (const auto& kv : genome.fa.contig_of) named[kv.second] = 1;
+      int32_t next = 0;
+      for (size_t r = 0; r < named.size(); r++)
+        if (named[r]) id_of_row[r] = next++;
+    }
+    auto ref_id = [&](const std::string& chr) {
+      const auto it = genome.fa.contig_of.find(chr);
+      return it == genome.fa.contig_of.end() ? -1 : id_of_row[it->second];
+    };
+    std::vector<VariantIn> in;
+    for (size_t q = 0; q < cfg.popu_names.size(); q++) {
+      const std::string& popu = cfg.popu_names[q];
+      auto each = [&](const auto& by_popu, auto make) {
+        const auto it = by_popu.find(popu);
+        if (it == by_popu.end()) return;
+        for (const auto& kv : it->second) {
+          const int32_t id = ref_id(kv.first);
+          for (const auto& v : kv.second) in.push_back(make(v, id));
+        }
+      };
+      each(genome.snvs, [&](const SNV& v, int32_t id) { return VariantIn{'s', id, (int64_t)v.pos, (int32_t)q, std::string(1, v.alt), 0}; });
+      each(genome.inserts, [&](const Insertion& v, int32_t id) { return VariantIn{'i', id, (int64_t)v.pos, (int32_t)q, v.seq, 0}; });
+      each(genome.dels, [&](const Deletion& v, int32_t id) { return VariantIn{'d', id, (int64_t)v.pos, (int32_t)q, std::string(), (int64_t)v.length}; });
+    }
+    for (const auto& kv : genome.snps) {
+      const int32_t id = ref_id(kv.first);
+      for (const SNP& v : kv.second) in.push_back(VariantIn{'p', id, (int64_t)v.pos, -1, std::string(1, v.nucleotide), 0});
+    }
+    std::vector<uint64_t> len;
+    for (const auto& r : truth_refs()) len.push_back(r.second);
+    vtable.build(in, len, cfg.popu_names.size());
+    st.variant_rows = vtable.rows.size();
+    st.variant_dropped = vtable.dropped;
+  }
+  void variants_begin() {
+    if (!opt.truth_variants || variants_begun) return;
+    auto t0 = Clock::now();
+    variants_build();
+    const std::vector<sg_variant> rows = vtable.abi();
+    eng.check(sg_variants_begin(eng.ctx, rows.data(), rows.size()), "sg_variants_begin");
+    variants_begun = true;
+    st.t_variants += since(t0);
+  }
+  void variants_open(const std::string& dir, const std::string& stem) {
+    if (!opt.truth_variants) return;
+    variants_begin();
+    auto t0 = Clock::now();
+    variants_stem = true;
+    if (opt.write_files) {
+      const std::string a = dir + "/" + stem + ".truth.variants.tsv";
+      fv = fopen(a.c_str(), "wb");
+      if (!fv) throw Error("Error: can not open file to save the true allele counts:\n" + a, -1);
+    }
+    st.t_variants += since(t0);
+  }
+  void variants_piece() {
+    auto t0 = Clock::now();
+    uint64_t rh = 0, h = 0;
+    eng.check(sg_variants_add(eng.ctx, &rh, &h), "sg_variants_add");
+    st.variant_hits += h;
+    st.t_variants += since(t0);
+  }
+  void variants_close() {
+    if (!variants_stem) return;
+    auto t0 = Clock::now();
+    variants_stem = false;
+    struct Closer { FILE*& f; ~Closer() { if (f) fclose(f); f = nullptr; } } closer{fv};
+    if (fv) {
+      std::vector<uint32_t> counts(vtable.rows.size() * 2 + 2);
+      uint64_t n = 0;
+      eng.check(sg_variants_counts(eng.ctx, counts.data(), vtable.rows.size(), &n), "sg_variants_counts");
+      std::vector<std::string> names;
+      for (const auto& r : truth_refs()) names.push_back(r.first);
+      const std::string text = vtable.format(names, cfg.popu_names, counts.data());
+      if (fwrite(text.data(), 1, text.size(), fv) != text.size()) throw Error("Error: short write to the true allele counts' file", -1);
+    }
+    eng.check(sg_variants_reset(eng.ctx), "sg_variants_reset");
+    st.t_variants += since(t0);
+  }
+
   void open_sink(const std::string& dir, const std::string& stem, bool paired, const std::string& suffix) {
     sink.open(dir, stem, paired, suffix, opt.gzip != 0);
     if (!opt.truth_bam) return;
@@ -310,7 +406,7 @@ struct Driver {
                                     plan.pieces.size(), plan.literals.data(), plan.literals.size(), plan.patches.data(),
                                     plan.patches.size()),
                 "sg_build_haplotypes");
-      if (opt.truth_bam || opt.truth_depth) {  // the copy list is the reads' way back to the reference: contig rows -> refIDs of the BAM header
+      if (opt.truth_bam || opt.truth_depth || opt.truth_variants) {  // the copy list is the reads' way back to the reference: contig rows -> refIDs of the BAM header
         const std::vector<int32_t> ref_ids = truth_ref_ids();
         eng.check(sg_truth_map(eng.ctx, plan.pieces.data(), plan.piece_seg_first.data(), plan.piece_seg_first.size(), ref_ids.data(), (uint32_t)ref_ids.size()),
                   "sg_truth_map");
@@ -671,6 +767,7 @@ struct Driver {
   bool prepare_batch(const std::string& popu, const std::string& chr) {
     if (!build_batch(popu, chr)) return false;
     depth_begin();   // (a session has no stems: its caller adds, reads and resets the depth itself)
+    variants_begin();
     plan_range(cur.a0, cur.a1);
     return true;
   }
@@ -729,6 +826,7 @@ struct Driver {
     st.fastq_bytes += n1 + n2;
     if (opt.truth_bam) truth_piece(sink);
     if (opt.truth_depth) depth_piece();
+    if (opt.truth_variants) variants_piece();
     if (!(opt.write_files || opt.fetch)) return;
     bool compressed = false;
     if (opt.gzip) {
@@ -866,6 +964,12 @@ struct Driver {
     if (opt.truth_depth && opt.shard_world > 1)
       throw Error("Error: --truth-depth cannot be combined with --world or --gpus above 1: the ranks' partial depths would have to "
                   "be summed, not concatenated");
+    if (opt.truth_variants && opt.host_haplotypes)
+      throw Error("Error: --truth-variants needs the haplotypes assembled on the device (their copy lists map the reads back to the "
+                  "reference); it cannot be combined with --host-haplotypes");
+    if (opt.truth_variants && opt.shard_world > 1)
+      throw Error("Error: --truth-variants cannot be combined with --world or --gpus above 1: the ranks' partial counts would have to "
+                  "be summed, not concatenated");
     cfg.load(config_path);
     seed = opt.has_seed ? opt.seed : (uint64_t)cfg.num["seed"];
     const int device = opt.device >= 0 ? opt.device : (int)cfg.num["device"];
@@ -937,6 +1041,7 @@ struct Driver {
     if (genome.mix_props.empty()) {
       if (opt.write_files) open_sink(out_dir, popus[0], paired, suffix);
       depth_open(out_dir, popus[0]);
+      variants_open(out_dir, popus[0]);
       set_read_counts(popus[0], reads);
       for (const std::string& chr : genome.chromosomes) run_batch(popus[0], chr, sink);
     } else {
@@ -951,8 +1056,10 @@ struct Driver {
         }
         drain_wait();  // the previous mixture's last batch still writes into the files about to be closed
         depth_close();
+        variants_close();
         if (opt.write_files) open_sink(out_dir, stem, paired, suffix);
         depth_open(out_dir, stem);
+        variants_open(out_dir, stem);
         for (size_t i = 0; i < popus.size(); i++) {
           const long popu_reads = (long)(reads * props[i] * acn[popus[i]] / w_acn);  // long*float is a float product (Genome.cpp:935)
           set_read_counts(popus[i], popu_reads);
@@ -962,6 +1069,7 @@ struct Driver {
     }
     drain_wait();
     depth_close();
+    variants_close();
     sink.close();
     log("\nReads generation done!\n");
     st.t_total = since(t_all);
@@ -1124,6 +1232,17 @@ extern "C" int simu_prepare_batch(simu_session* s, int popu, int chr, int* has_w
   return session_guard(err, err_len, [&]() {
     bool w = s->d.prepare_batch(s->d.cfg.popu_names.at(popu), s->d.genome.chromosomes.at(chr));
     if (has_work) *has_work = w ? 1 : 0;
+  });
+}
+extern "C" int simu_variant_table(simu_session* s, void* rows, uint64_t cap, uint64_t* n, char* err, size_t err_len) {
+  return session_guard(err, err_len, [&]() {
+    if (!s || !n) throw simu::Error("simu_variant_table: no session");
+    if (!s->d.opt.truth_variants) throw simu::Error("simu_variant_table: the session was not opened with truth_variants");
+    s->d.variants_build();
+    const std::vector<sg_variant> a = s->d.vtable.abi();
+    *n = a.size();
+    const uint64_t m = std::min<uint64_t>(cap, a.size());
+    if (rows && m) memcpy(rows, a.data(), (size_t)m * sizeof(sg_variant));
   });
 }
 extern "C" void simu_get_stats(simu_session* s, simu_stats* st) { if (s && st) *st = s->d.st; }

@@ -43,6 +43,10 @@ typedef struct simu_options {
                            //    records are made and compressed on the device, piece by piece, in FASTQ order); needs the
                            //    device-assembled haplotypes (refused with host_haplotypes).  Sharded runs write parts like the
                            //    FASTQ parts: rank 0's carries the header, the last rank's the BGZF end-of-file block
+  int32_t truth_variants;  // 1: write per variant of the variation and SNP files how many reads cover the site and how many
+                           //    carry the allele to <stem>.truth.variants.tsv beside the FASTQ files (sg_variants_*; the
+                           //    rule: DESIGN.md "True allele counts"), summed like truth_depth.  Needs the device-assembled
+                           //    haplotypes; refused in a sharded run (partial counts would have to be summed)
   int32_t truth_depth;     // BIN >= 1: write the reads' true coverage to <stem>.truth.depth.bedgraph beside the FASTQ files
                            //    (sg_depth_*: every M base of every read's true alignment, summed over the pieces, chromosomes
                            //    and populations written into the stem); BIN 1: one row per run of equal depth, BIN > 1: the
@@ -80,6 +84,10 @@ typedef struct simu_stats {
   uint64_t truth_bytes;    // ... bytes of the record stream and of its BGZF members (header and end-of-file block aside)
   uint64_t truth_bgzf_bytes;
   double t_truth;          // sg_truth_bam calls + fetching and writing their members (synchronous, per piece)
+  uint64_t variant_rows;   // truth_variants: rows of the variant table, ...
+  uint64_t variant_dropped;  // ... input rows left out of it (a contig the FASTA does not hold, a position outside it, no length)
+  uint64_t variant_hits;   // ... counts of `total` over all rows and stems
+  double t_variants;       // building the table, sg_variants_* calls, formatting and writing the rows
   uint64_t depth_bases;    // truth_depth: M bases added to the depth, ...
   uint64_t depth_rows;     // ... bedGraph lines made (written unless write_files == 0)
   double t_depth;          // sg_depth_* calls, formatting and writing the rows
@@ -110,6 +118,24 @@ int simu_selftest_haplotypes(const char* config_path, uint64_t seed, char* err, 
 // does not describe a contig of ln bases.
 uint64_t simu_depth_format(const char* name, uint64_t ln, uint64_t bin, const void* data, uint64_t n, char* out, uint64_t cap, uint64_t* rows);
 
+// A --truth-variants file from raw variant rows, host only: the table is built as the driver builds it and written with
+// the counts given.  Contigs are the n_contigs names / lengths in BAM refID order, populations the n_popus names in
+// config order.  Input row i: kind[i] 's' (variation-file SNV), 'p' (SNP-file row), 'i', 'd'; contig[i] a contig name
+// (one not listed: the row is dropped); pos[i] the file's 1-based position; popu[i] the population's index ('p' rows: any);
+// text[i] the alt base, the inserted sequence or the deletion length in decimal.  Rows merge on (contig, pos - 1,
+// upper-case allele) for s / p, (contig, pos - 1, length) for i (the first sequence met is written) and d; rows with
+// pos - 1 outside [0, LN) or a length below 1 are dropped.  Order: refID, position, type (s / p, i, d), allele byte or
+// length.  The file: the header line "#chrom\tpos\ttype\tallele\talt_reads\ttotal_reads\tpopulations", then one line per
+// table row, `type` s when a variation-file row lists the allele, else p; `populations` comma-joined in config order, `.`
+// for p.  counts: [rows][2] uint32 (alt, total), or NULL for zeros; n_counts must then be the table's rows (UINT64_MAX
+// otherwise, and *rows still says how many there are).  table: when not NULL, room for table_cap sg_variant rows (simuscop_amd.h), filled
+// with the table as sg_variants_begin takes it when it fits.  The text is written to out[0 .. cap) when it fits; returns
+// its length.
+uint64_t simu_variants_format(const char* const* contig_name, const uint64_t* contig_len, uint32_t n_contigs, const char* const* popu_name,
+                              uint32_t n_popus, const char* kind, const char* const* contig, const int64_t* pos, const int32_t* popu,
+                              const char* const* text, uint64_t n_in, const uint32_t* counts, uint64_t n_counts, void* table,
+                              uint64_t table_cap, char* out, uint64_t cap, uint64_t* rows, uint64_t* dropped);
+
 // ---- step-by-step session (bench.py / multi-GPU launcher) ----
 typedef struct simu_session simu_session;
 int simu_open(const char* config_path, const simu_options* opt, simu_session** out, char* err, size_t err_len);
@@ -121,6 +147,9 @@ int simu_weighted_length(simu_session* s, int popu, double* wl, char* err, size_
 int simu_set_reads(simu_session* s, int popu, int64_t reads, char* err, size_t err_len);
 int simu_prepare_batch(simu_session* s, int popu, int chr, int* has_work, char* err, size_t err_len);
 void simu_get_stats(simu_session* s, simu_stats* st);
+// the variant table of a session opened with truth_variants (the one given to sg_variants_begin at the first
+// simu_prepare_batch): *n = rows; the first min(cap, *n) are written
+int simu_variant_table(simu_session* s, void* rows /* sg_variant[cap] */, uint64_t cap, uint64_t* n, char* err, size_t err_len);
 uint64_t simu_batch_slots(simu_session* s);  // planned fragment slots of the prepared batch (sg_truth_reads addresses reads by slot)
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 // sg_api.h -- what the files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
 // sink, reference, haplotypes, window planner), sg_api_train.cpp (profile training, BGZF / BAM input) and
-// sg_api_depth.cpp (true coverage).  Internal: the
+// sg_api_depth.cpp (true coverage) and sg_api_variants.cpp (true allele counts).  Internal: the
 // ABI itself is include/simuscop_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -84,6 +84,14 @@ struct sg_ctx {
     int64_t scanned = -1;
   } depth;
   DevBuf depth_diff, depth_meta, depth_work, depth_out;
+  // true allele counts (sg_variants_*, sg_api_variants.cpp): var_rows holds the sorted table as sg::VariantRow rows,
+  // var_counts the [n][2] uint32 counters (total, alt) and behind them the kernel's three 64-bit counters.  Without
+  // sg_variants_begin nothing is kept and nothing is allocated.
+  struct Variants {
+    bool on = false;
+    uint64_t n = 0, reads_hit = 0, hits = 0;
+  } variants;
+  DevBuf var_rows, var_counts;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // device-made sampling plan: window weights per store id (sg_windows_build), the batch table of sg_plan_windows
   std::map<uint32_t, DevBuf> wstore;

@@ -251,4 +251,114 @@ void launch_depth_bins(const DepthView& V, const uint64_t* tile_base, uint32_t b
 void launch_depth_runs(const DepthView& V, const uint64_t* tile_base, const uint64_t* start_base, DepthRun* rows, uint64_t cap, hipStream_t s);
 void launch_depth_fetch(const DepthView& V, const uint64_t* tile_base, uint32_t first, uint32_t n, uint32_t* out, hipStream_t s);
 
+// ---- true allele counts per variant (simuReads --truth-variants; kernel: sg_variants.hip) ----
+// One row of the variant table as the scan reads it: 16 bytes, sorted by key.  kind 0 SNV (len unused), 1 insertion of
+// `len` bases behind base p, 2 deletion of bases [p, p + len).
+struct VariantRow {
+  uint64_t key;        // BAM refID << 32 | p (0-based on the contig)
+  uint32_t len;
+  uint32_t kind_code;  // kind | the allele's base code << 8 (SNV rows)
+};
+__host__ __device__ inline uint64_t variant_key(uint32_t contig, uint64_t p) { return ((uint64_t)contig << 32) | (p & 0xFFFFFFFFull); }
+// the chains' base codes (encode_base, sg_haplotypes.hip) for an allele given as a letter
+__host__ __device__ inline uint32_t variant_base_code(uint32_t b) {
+  switch (b & 0xDFu) {
+    case 'A': return 0u;
+    case 'C': return 1u;
+    case 'T': return 2u;
+    case 'G': return 3u;
+    case 'N': return 4u;
+    case 'X': return 6u;
+    default: return 5u;
+  }
+}
+// first row of [0, n) whose key is not below `key`
+__host__ __device__ inline uint64_t variant_lower_bound(const VariantRow* table, uint64_t n, uint64_t key) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (table[mid].key < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// The counting rule (DESIGN.md "True allele counts").  The template is `L` chain bases from `tmpl_off` on, `pieces` its
+// chain's pieces in offset order ([0, n_pieces) may hold further chains behind it: the walk stops at the template's
+// end), `pi` the index of the piece that holds tmpl_off.  `codes[o - codes_off]` is the chain's base code at chain
+// offset o; it is read for SNV rows only.  The walk goes piece by piece: every reference piece is clipped to the
+// template, the table is searched once for the clipped span [a, b) of its contig, and the rows with p in [a, b] are
+// visited -- a base at x can touch the SNV and insertion rows at x and the deletion rows at x + 1 (a deletion is
+// anchored on the base in front of it).  Pairs of neighbours inside a piece are reference neighbours; the pair across
+// the clipped piece's end is resolved against the next piece that holds a base.  `hit(row, is_alt)` is called once
+// per count of `total`.
+template <class Hit>
+__host__ __device__ inline void truth_variant_scan(const TruthPiece* pieces, uint64_t n_pieces, uint64_t pi, uint64_t tmpl_off, uint32_t L,
+                                                   const uint8_t* codes, uint64_t codes_off, const VariantRow* table, uint64_t n_rows,
+                                                   Hit hit) {
+  if (!n_rows || !L) return;
+  const uint64_t t_end = tmpl_off + L;
+  for (uint64_t j = pi; j < n_pieces && pieces[j].dst < t_end; j++) {
+    const TruthPiece& p = pieces[j];
+    if ((p.meta >> 30) & 1u) continue;   // no clause is anchored on a literal base
+    const uint64_t ca = p.dst > tmpl_off ? p.dst : tmpl_off, pe = p.dst + p.len, cb = pe < t_end ? pe : t_end;
+    if (ca >= cb) continue;
+    const uint32_t contig = p.meta & 0x3FFFFFFFu;
+    const uint64_t a = p.src + (ca - p.dst), b = a + (cb - ca);
+    uint64_t r = variant_lower_bound(table, n_rows, variant_key(contig, a));
+    const uint64_t key_end = variant_key(contig, b);
+    if (r >= n_rows || table[r].key > key_end) continue;
+    // what follows the clipped piece's last base: nothing (the template ends there), a reference base, or a literal
+    // piece -- of `nx_len` bases, `nx_whole` when it lies inside the template with one more template base behind it
+    bool nx_any = false, nx_lit = false, nx_whole = false;
+    uint32_t nx_contig = 0, nx_len = 0;
+    uint64_t nx_pos = 0;
+    if (cb < t_end) {
+      uint64_t q = j + 1;
+      while (q < n_pieces && pieces[q].len == 0u) q++;
+      if (q < n_pieces && pieces[q].dst == cb) {
+        const TruthPiece& nx = pieces[q];
+        nx_any = true;
+        nx_lit = (nx.meta >> 30) & 1u;
+        nx_contig = nx.meta & 0x3FFFFFFFu;
+        nx_pos = nx.src;
+        nx_len = nx.len;
+        nx_whole = nx.dst + nx.len < t_end;
+      }
+    }
+    for (; r < n_rows && table[r].key <= key_end; r++) {
+      const VariantRow row = table[r];
+      const uint64_t pos = row.key & 0xFFFFFFFFull;
+      const uint32_t kind = row.kind_code & 0xFFu;
+      if (kind == 0u) {
+        if (pos < b) hit(r, (uint32_t)codes[ca + (pos - a) - codes_off] == (row.kind_code >> 8));
+      } else if (kind == 1u) {
+        if (pos >= b) continue;
+        if (pos + 1 < b) hit(r, false);
+        else if (nx_any) {
+          if (!nx_lit) { if (nx_contig == contig && nx_pos == pos + 1) hit(r, false); }
+          else if (nx_whole && nx_len == row.len) hit(r, true);
+        }
+      } else {
+        if (pos <= a) continue;          // anchored on base pos - 1 (a row with p = 0 has none)
+        if (pos < b) hit(r, false);
+        else if (nx_any && !nx_lit && nx_contig == contig) {
+          if (nx_pos == pos) hit(r, false);
+          else if (nx_pos == pos + row.len) hit(r, true);
+        }
+      }
+    }
+  }
+}
+
+struct VariantJob {
+  const TruthPiece* pieces;
+  const uint64_t* chain_first;
+  uint32_t n_chains, n_reads;
+  const VariantRow* table;
+  uint64_t n_rows;
+  uint32_t* counts;              // [n_rows][2]: total, alt
+  unsigned long long* counters;  // [0] reads with a hit, [1] hits, [2] flags: 1 a template whose first piece was not found
+};
+void launch_variants_add(const DevProfile& P, const DevBatch& B, const VariantJob& J, hipStream_t s);
+
 }  // namespace sg
