@@ -461,6 +461,61 @@ int sg_variants_end(sg_ctx* ctx);
 int sg_variant_observe(const sg_truth_piece* pieces, uint64_t n_pieces, const uint8_t* codes, uint64_t tmpl_off, uint32_t tmpl_len,
                        const sg_variant* rows, uint64_t n_rows, uint32_t* hit_row, uint8_t* hit_alt, uint64_t cap, uint64_t* n_hits);
 
+/* ---- true error counts: per mate, cycle and reported quality, how many bases were really wrong
+ * (simuReads --truth-errors) ----
+ * A read is compared with its template, the read-length haplotype bases it was cut from, not with the reference, so a
+ * variant allele is no error and no piece map is needed.  In read direction the template is T'[0 .. L): the chain codes
+ * (sg_haplotype_codes form: A0 C1 T2 G3, N 4, other 5, X 6) as they stand for a forward read, in reverse order and
+ * complemented (code ^ 2 below 4) for a reverse one.  The read's events (ev_pack words, read direction, ascending) are
+ * laid over it as Profile::predict applies them.  Walk j from 0 with read position r = 0:
+ *   deletion of k at j (k clipped to L - j)   no read base; row D(mate, j): events += 1, bases += k; j += k
+ *   otherwise read base r pairs with T'[j]    T'[j] in A/C/G/T: bases++ at (mate, r, quality), errors++ as well when the
+ *                                             read's letter differs (an N is an error), S(mate, T'[j], letter)++;
+ *                                             else other++ at (mate, r, quality); r++, j++
+ *   insertion of k behind that base           the next k read bases: inserted++ at their (mate, r, quality), no verdict;
+ *                                             row I(mate, j): events += 1, bases += k; r += k
+ * At the end r must be the read's length.  Quality is the text byte minus 33; mate is 0 / 1 (0 for SE).  A live read
+ * whose template does not lie in its chain counts nowhere (`skipped`).  The table is flat, uint64, in this order:
+ *   Q [2][cycles][n_qual][4]   bases, errors, other, inserted; quality column q is quality qual_lo + q
+ *   S [2][4][5]                from A C T G, to A C T G N
+ *   I [2][L][2], D [2][L][2]   events, bases
+ * 8 * cycles * n_qual + 40 + 8 * L cells, L the profile's read length.  Additive: a context that never calls
+ * sg_errtab_begin launches no kernel of this part and holds no device memory for it; every call below before
+ * sg_errtab_begin is SG_ERR_INVALID.
+ *   sg_errtab_begin     after a profile is loaded; cycles in [L, 65535] (L plus what SG_MAX_EVENTS insertions can add),
+ *                       n_qual in [1, 128], qual_lo + n_qual < 224; allocates and zeroes (a second call replaces the state)
+ *   sg_errtab_add       after sg_result: counts the current pass's reads; *bases / *errors = what it added to those two
+ *                       columns.  Refuses a pass that ran under SG_DIAG.  A read whose events do not end at its length
+ *                       or lie outside its template (SG_ERR_INVALID), a read longer than `cycles` (SG_ERR_OVERFLOW) and a
+ *                       quality byte outside the range (SG_ERR_INVALID; that base alone) are not counted and fail the
+ *                       call.  A failed call adds nothing to the sums and returns no counts; the table may hold a part of
+ *                       the pass and is undefined until sg_errtab_reset
+ *   sg_errtab_counts    copies the table out; *n = cells; cap == 0 gives the size alone; SG_ERR_OVERFLOW when 0 < cap < *n
+ *   sg_errtab_reset     zeroes the table and the sums, keeps the buffer
+ *   sg_errtab_info      sizes, sums since sg_errtab_begin / sg_errtab_reset, and how the kernel stages the table
+ *   sg_errtab_end       frees everything
+ *   sg_errtab_observe   host only, no context: the same rule for one read, added into `table` (`cells` must be the
+ *                       size above for tmpl_len = L).  codes[i] is the chain's code of template base i in chain
+ *                       direction.  A refused read (as for sg_errtab_add; also a quality byte below 33 + qual_lo, an
+ *                       event of length 0 or out of order) adds nothing                                              */
+typedef struct sg_errtab_shape {
+  uint32_t cycles, qual_lo, n_qual, tmpl_len;
+  uint64_t cells;
+  uint64_t bases, errors;   /* sums of the two columns over both mates */
+  uint64_t skipped, reads;  /* live reads outside their chain; reads counted */
+  uint32_t win_cycles;      /* cycles a workgroup stages in LDS, ... */
+  uint32_t lds_bytes;       /* ... and the bytes that takes */
+} sg_errtab_shape;
+int sg_errtab_begin(sg_ctx* ctx, uint32_t cycles, uint32_t qual_lo, uint32_t n_qual);
+int sg_errtab_add(sg_ctx* ctx, uint64_t* bases, uint64_t* errors);
+int sg_errtab_counts(sg_ctx* ctx, uint64_t* out, uint64_t cap, uint64_t* n);
+int sg_errtab_reset(sg_ctx* ctx);
+int sg_errtab_info(sg_ctx* ctx, sg_errtab_shape* out);
+int sg_errtab_end(sg_ctx* ctx);
+int sg_errtab_observe(const uint8_t* codes, uint32_t tmpl_len, int reverse, const uint32_t* events, uint32_t n_events, const char* bases,
+                      const char* quals, uint32_t read_len, uint32_t mate, uint32_t cycles, uint32_t qual_lo, uint32_t n_qual, uint64_t* table,
+                      uint64_t cells);
+
 /* When enabled, HIP events bracket every kernel of sg_sample on the ctx's stream;
  * sg_kernel_times() then returns the last pass's per-kernel milliseconds (after sg_result).     */
 int sg_set_profiling(sg_ctx* ctx, int enable);

@@ -36,6 +36,7 @@ ENGINE_SYMBOLS = [
     "sg_depth_info", "sg_depth_end",
     "sg_variants_begin", "sg_variants_add", "sg_variants_counts", "sg_variants_reset", "sg_variants_info", "sg_variants_end",
     "sg_variant_observe",
+    "sg_errtab_begin", "sg_errtab_add", "sg_errtab_counts", "sg_errtab_reset", "sg_errtab_info", "sg_errtab_end", "sg_errtab_observe",
 ]
 
 
@@ -119,6 +120,13 @@ class SgVariant(C.Structure):
     _fields_ = [("contig", C.c_uint32), ("kind", C.c_uint32), ("pos", C.c_uint64), ("len", C.c_uint32), ("allele", C.c_uint32)]
 
 
+class SgErrtabShape(C.Structure):
+    """sg_errtab_shape: sizes, sums and staging of the true error counts (sg_errtab_info)"""
+    _fields_ = [("cycles", C.c_uint32), ("qual_lo", C.c_uint32), ("n_qual", C.c_uint32), ("tmpl_len", C.c_uint32), ("cells", C.c_uint64),
+                ("bases", C.c_uint64), ("errors", C.c_uint64), ("skipped", C.c_uint64), ("reads", C.c_uint64),
+                ("win_cycles", C.c_uint32), ("lds_bytes", C.c_uint32)]
+
+
 class SgHapPatch(C.Structure):
     _fields_ = [("dst", C.c_uint64), ("chain", C.c_uint32), ("base", C.c_uint32)]
 
@@ -129,7 +137,7 @@ class SimuOptions(C.Structure):
                 ("output_dir", C.c_char_p), ("repeat_sample", C.c_int32), ("host_haplotypes", C.c_int32), ("gzip", C.c_int32),
                 ("shard_contigs", C.c_int32), ("no_eof_block", C.c_int32), ("exchange", C.c_void_p), ("exchange_user", C.c_void_p),
                 ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32),
-                ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
+                ("truth_errors", C.c_int32), ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
 
 
 # simu_options.exchange: all-reduce(sum) of n doubles over the ranks, in place
@@ -153,6 +161,7 @@ class SimuStats(C.Structure):
                 ("emit_clean_cap", C.c_uint32),
                 ("truth_records", C.c_uint64), ("truth_unmapped", C.c_uint64), ("truth_bytes", C.c_uint64),
                 ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double),
+                ("errors_bases", C.c_uint64), ("errors_subst", C.c_uint64), ("t_errors", C.c_double),
                 ("variant_rows", C.c_uint64), ("variant_dropped", C.c_uint64), ("variant_hits", C.c_uint64), ("t_variants", C.c_double),
                 ("depth_bases", C.c_uint64), ("depth_rows", C.c_uint64), ("t_depth", C.c_double)]
 
@@ -265,6 +274,14 @@ def load_engine():
     lib.sg_variants_end.argtypes = [vp]
     lib.sg_variant_observe.argtypes = [C.POINTER(SgTruthPiece), C.c_uint64, u8p, C.c_uint64, C.c_uint32, C.POINTER(SgVariant), C.c_uint64,
                                        u32p, u8p, C.c_uint64, u64p]
+    lib.sg_errtab_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.sg_errtab_add.argtypes = [vp, u64p, u64p]
+    lib.sg_errtab_counts.argtypes = [vp, u64p, C.c_uint64, u64p]
+    lib.sg_errtab_reset.argtypes = [vp]
+    lib.sg_errtab_info.argtypes = [vp, C.POINTER(SgErrtabShape)]
+    lib.sg_errtab_end.argtypes = [vp]
+    lib.sg_errtab_observe.argtypes = [u8p, C.c_uint32, C.c_int, u32p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, u64p, C.c_uint64]
     _engine = lib
     return lib
 
@@ -308,6 +325,8 @@ def load_host():
                                          u64p, u64p]
     lib.simu_variants_format.restype = C.c_uint64
     lib.simu_variant_table.argtypes = [vp, C.c_void_p, C.c_uint64, u64p, C.c_char_p, C.c_size_t]
+    lib.simu_errors_format.argtypes = [u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, u64p]
+    lib.simu_errors_format.restype = C.c_uint64
     _host = lib
     return lib
 
@@ -485,6 +504,45 @@ def variants_format(contigs, populations, rows, counts=None, want_table: bool = 
     if want_table:
         res += ([(v.contig, v.kind, v.pos, v.len, v.allele) for v in tab[:n_rows.value]],)
     return res
+
+
+def errors_cells(cycles: int, n_qual: int, tmpl_len: int) -> int:
+    """Cells of the true error counts' flat table (sg_errtab_counts): Q [2][cycles][n_qual][4] (bases, errors, other,
+    inserted) | S [2][4][5] (from A C T G, to A C T G N) | I [2][L][2] | D [2][L][2] (events, bases)."""
+    return 8 * cycles * n_qual + 40 + 8 * tmpl_len
+
+
+def errors_observe(table, codes, reverse: bool, events, bases: bytes, quals: bytes, mate: int, cycles: int, qual_lo: int, n_qual: int) -> None:
+    """sg_errtab_observe (host only, no GPU): add what one read counts into `table`, a contiguous numpy uint64 array of
+    errors_cells(cycles, n_qual, len(codes)) cells.  `codes`: the template's chain base codes (A0 C1 T2 G3, N 4 ...) in chain
+    direction, a numpy uint8 array or a sequence; `events`: ev_pack words in read direction; `mate` 0 / 1.  A refused read
+    raises SimuError and adds nothing."""
+    lib = load_engine()
+    if hasattr(codes, "ctypes"):
+        cod = codes.ctypes.data_as(C.POINTER(C.c_uint8))
+    else:
+        cod = (C.c_uint8 * max(len(codes), 1))(*[int(c) for c in codes])
+    ev = (C.c_uint32 * max(len(events), 1))(*[int(e) for e in events])
+    if len(bases) != len(quals):
+        raise ValueError("errors_observe: bases and qualities differ in length")
+    rc = lib.sg_errtab_observe(cod, len(codes), 1 if reverse else 0, ev, len(events), bytes(bases), bytes(quals), len(bases), mate, cycles, qual_lo,
+                               n_qual, table.ctypes.data_as(C.POINTER(C.c_uint64)), table.size)
+    if rc != 0:
+        raise SimuError(f"sg_errtab_observe refused the read (code {rc})")
+
+
+def errors_format(table, cycles: int, qual_lo: int, n_qual: int, tmpl_len: int, mates: int):
+    """simu_errors_format (host only, no GPU): the text of a --truth-errors file made of a table in sg_errtab_counts'
+    layout (a contiguous numpy uint64 array).  Returns (text, data lines)."""
+    lib = load_host()
+    rows = C.c_uint64()
+    ptr = table.ctypes.data_as(C.POINTER(C.c_uint64))
+    need = lib.simu_errors_format(ptr, table.size, cycles, qual_lo, n_qual, tmpl_len, mates, None, 0, C.byref(rows))
+    if need == 2 ** 64 - 1:
+        raise SimuError("simu_errors_format: the table does not have the size these dimensions give, or mates is not 1 or 2")
+    buf = C.create_string_buffer(max(int(need), 1))
+    lib.simu_errors_format(ptr, table.size, cycles, qual_lo, n_qual, tmpl_len, mates, buf, need, C.byref(rows))
+    return buf.raw[:need], rows.value
 
 
 class Session:
@@ -706,6 +764,38 @@ class Session:
 
     def variants_end(self) -> None:
         self._sg(self.eng.sg_variants_end(self.ctx), "sg_variants_end")
+
+    # ---- true error counts (sessions opened with truth_errors=1: the driver begins the table with the profile's cycle
+    # capacity and quality range at the first prepare_batch; errors_begin starts over with the caller's) ----
+    def errors_begin(self, cycles: int, qual_lo: int, n_qual: int) -> None:
+        self._sg(self.eng.sg_errtab_begin(self.ctx, cycles, qual_lo, n_qual), "sg_errtab_begin")
+
+    def errors_add(self):
+        """Count the reads of the last pass (after result()); returns (bases, errors) added to those two columns."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._sg(self.eng.sg_errtab_add(self.ctx, C.byref(a), C.byref(b)), "sg_errtab_add")
+        return a.value, b.value
+
+    def errors_counts(self):
+        """The flat table (numpy uint64, errors_cells(...) cells)."""
+        import numpy as np
+        n = C.c_uint64()
+        self._sg(self.eng.sg_errtab_counts(self.ctx, None, 0, C.byref(n)), "sg_errtab_counts")
+        out = np.zeros(n.value, dtype=np.uint64)
+        self._sg(self.eng.sg_errtab_counts(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint64)), n.value, C.byref(n)), "sg_errtab_counts")
+        return out
+
+    def errors_reset(self) -> None:
+        self._sg(self.eng.sg_errtab_reset(self.ctx), "sg_errtab_reset")
+
+    def errors_info(self) -> SgErrtabShape:
+        """sg_errtab_shape: cycles, qual_lo, n_qual, tmpl_len, cells, sums since errors_begin / errors_reset, staging."""
+        out = SgErrtabShape()
+        self._sg(self.eng.sg_errtab_info(self.ctx, C.byref(out)), "sg_errtab_info")
+        return out
+
+    def errors_end(self) -> None:
+        self._sg(self.eng.sg_errtab_end(self.ctx), "sg_errtab_end")
 
     def emit_info(self):
         """(items handed to the generic item code, whether the batch was re-emitted) of the last pass."""

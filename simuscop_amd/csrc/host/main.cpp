@@ -5,6 +5,8 @@
 //   --truth-depth BIN   the reads' true coverage as <stem>.truth.depth.bedgraph (BIN 1: runs of equal depth; BIN > 1: means)
 //   --truth-variants    per variant of the variation and SNP files the reads that cover the site and those that carry the
 //                       allele, as <stem>.truth.variants.tsv
+//   --truth-errors      per mate, cycle and reported quality how many bases were really wrong (the read against the haplotype
+//                       bases it was cut from), a substitution matrix and the sequencing indels, as <stem>.truth.errors.tsv
 //   --gpus N [--shard-contigs]
 //   --crlf-as-lf  --strict-bases  --unique-contigs   (each turns one kept reference quirk off: simulate.h)
 #include <dirent.h>
@@ -241,6 +243,7 @@ int main(int argc, char* argv[]) {
       opt.truth_depth = (int32_t)bin;
     }
     else if (a == "--truth-variants") opt.truth_variants = 1;
+    else if (a == "--truth-errors") opt.truth_errors = 1;
     else if (a == "--shard-contigs") opt.shard_contigs = 1;
     else if (a == "--no-eof-block") opt.no_eof_block = 1;
     else if (a == "--crlf-as-lf") opt.crlf_as_lf = 1;
@@ -268,6 +271,11 @@ int main(int argc, char* argv[]) {
   }
   if (opt.truth_variants && (gpus > 1 || opt.shard_world > 1)) {
     std::cerr << "Error: --truth-variants cannot be combined with --world or --gpus above 1: the ranks' partial counts would have to be "
+                 "summed, not concatenated" << std::endl;
+    return 1;
+  }
+  if (opt.truth_errors && (gpus > 1 || opt.shard_world > 1)) {
+    std::cerr << "Error: --truth-errors cannot be combined with --world or --gpus above 1: the ranks' partial tables would have to be "
                  "summed, not concatenated" << std::endl;
     return 1;
   }
@@ -302,7 +310,8 @@ int main(int argc, char* argv[]) {
             "plan %.3fs sample %.3fs (haplotype calls %.3fs sg_plan %.3fs) fetch %.3fs write %.3fs total %.3fs | kernels ms: plan %.3f namebase %.3f indel %.3f scan %.3f emit %.3f emit_slow %.3f | queued_items=%llu requeued_batches=%llu emit_kernel=%d slow_rows_lds=%d emit_lds=%u clean_cap=%u | compress %.3fs gz_bytes=%llu | "
             "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f | "
             "variant_rows=%llu variant_dropped=%llu variant_hits=%llu variants_s=%.3f | "
-            "depth_bases=%llu depth_rows=%llu depth_s=%.3f\n",
+            "depth_bases=%llu depth_rows=%llu depth_s=%.3f | "
+            "errors_bases=%llu errors_subst=%llu errors_s=%.3f\n",
             (unsigned long long)st.reads, (unsigned long long)st.fragments, (unsigned long long)st.fastq_bytes,
             (unsigned long long)st.windows, (unsigned long long)st.segments, (unsigned long long)st.batches, st.t_load,
             st.t_engine, st.t_reference,
@@ -312,6 +321,7 @@ int main(int argc, char* argv[]) {
             st.emit_clean_cap, st.t_compress, (unsigned long long)st.gz_bytes, (unsigned long long)st.truth_records,
             (unsigned long long)st.truth_unmapped, (unsigned long long)st.truth_bytes, (unsigned long long)st.truth_bgzf_bytes, st.t_truth,
             (unsigned long long)st.variant_rows, (unsigned long long)st.variant_dropped, (unsigned long long)st.variant_hits, st.t_variants,
-            (unsigned long long)st.depth_bases, (unsigned long long)st.depth_rows, st.t_depth);
+            (unsigned long long)st.depth_bases, (unsigned long long)st.depth_rows, st.t_depth,
+            (unsigned long long)st.errors_bases, (unsigned long long)st.errors_subst, st.t_errors);
   return 0;
 }

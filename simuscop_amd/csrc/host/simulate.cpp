@@ -25,6 +25,7 @@
 
 #include "../../../include/simuscop_amd.h"
 #include "genome.h"
+#include "truth_errors.h"
 #include "truth_variants.h"
 
 namespace simu {
@@ -386,6 +387,61 @@ struct Driver {
     }
     eng.check(sg_variants_reset(eng.ctx), "sg_variants_reset");
     st.t_variants += since(t0);
+  }
+
+  // ---- --truth-errors ----
+  // The table lives on the device from the first stem on; every piece counts its reads (errors_piece), a stem's file is
+  // made of the table when the stem closes (errors_format, truth_errors.h) and the table is zeroed for the next stem.
+  // The reads are compared with their haplotype templates, so no piece map is involved.
+  bool errors_begun = false, errors_stem = false;
+  FILE* fe = nullptr;   // <stem>.truth.errors.tsv
+  sg_errtab_shape errors_shape{};
+  void errors_begin() {
+    if (!opt.truth_errors || errors_begun) return;
+    // cycles: the template plus what SG_MAX_EVENTS insertions of the longest kind can add; qualities: the profile's
+    // alphabet, at least the 21 an N draws from (Profile::predict)
+    const uint32_t L = (uint32_t)prof.read_length, max_ins = prof.ins_cdf.empty() ? 0u : (uint32_t)prof.ins_cdf.size() - 1u;
+    const uint32_t cycles = (uint32_t)std::min<uint64_t>(0xFFFFu, (uint64_t)L + (uint64_t)SG_MAX_EVENTS * max_ins);
+    const uint32_t qual_lo = (uint32_t)std::max(0, prof.min_qual - 33), n_qual = (uint32_t)std::max(prof.n_qual, 21);
+    eng.check(sg_errtab_begin(eng.ctx, cycles, qual_lo, n_qual), "sg_errtab_begin");
+    eng.check(sg_errtab_info(eng.ctx, &errors_shape), "sg_errtab_info");
+    errors_begun = true;
+  }
+  void errors_open(const std::string& dir, const std::string& stem) {
+    if (!opt.truth_errors) return;
+    auto t0 = Clock::now();
+    errors_begin();
+    errors_stem = true;
+    if (opt.write_files) {
+      const std::string a = dir + "/" + stem + ".truth.errors.tsv";
+      fe = fopen(a.c_str(), "wb");
+      if (!fe) throw Error("Error: can not open file to save the true error counts:\n" + a, -1);
+    }
+    st.t_errors += since(t0);
+  }
+  void errors_piece() {
+    auto t0 = Clock::now();
+    uint64_t b = 0, e = 0;
+    eng.check(sg_errtab_add(eng.ctx, &b, &e), "sg_errtab_add");
+    st.errors_bases += b;
+    st.errors_subst += e;
+    st.t_errors += since(t0);
+  }
+  void errors_close() {
+    if (!errors_stem) return;
+    auto t0 = Clock::now();
+    errors_stem = false;
+    struct Closer { FILE*& f; ~Closer() { if (f) fclose(f); f = nullptr; } } closer{fe};
+    if (fe) {
+      std::vector<uint64_t> table(errors_shape.cells);
+      uint64_t n = 0;
+      eng.check(sg_errtab_counts(eng.ctx, table.data(), table.size(), &n), "sg_errtab_counts");
+      const std::string text = errors_format(table.data(), errors_shape.cycles, errors_shape.qual_lo, errors_shape.n_qual, errors_shape.tmpl_len,
+                                             cfg.paired() ? 2u : 1u, nullptr);
+      if (fwrite(text.data(), 1, text.size(), fe) != text.size()) throw Error("Error: short write to the true error counts' file", -1);
+    }
+    eng.check(sg_errtab_reset(eng.ctx), "sg_errtab_reset");
+    st.t_errors += since(t0);
   }
 
   void open_sink(const std::string& dir, const std::string& stem, bool paired, const std::string& suffix) {
@@ -768,6 +824,7 @@ struct Driver {
     if (!build_batch(popu, chr)) return false;
     depth_begin();   // (a session has no stems: its caller adds, reads and resets the depth itself)
     variants_begin();
+    errors_begin();
     plan_range(cur.a0, cur.a1);
     return true;
   }
@@ -827,6 +884,7 @@ struct Driver {
     if (opt.truth_bam) truth_piece(sink);
     if (opt.truth_depth) depth_piece();
     if (opt.truth_variants) variants_piece();
+    if (opt.truth_errors) errors_piece();
     if (!(opt.write_files || opt.fetch)) return;
     bool compressed = false;
     if (opt.gzip) {
@@ -970,6 +1028,9 @@ struct Driver {
     if (opt.truth_variants && opt.shard_world > 1)
       throw Error("Error: --truth-variants cannot be combined with --world or --gpus above 1: the ranks' partial counts would have to "
                   "be summed, not concatenated");
+    if (opt.truth_errors && opt.shard_world > 1)
+      throw Error("Error: --truth-errors cannot be combined with --world or --gpus above 1: the ranks' partial tables would have to "
+                  "be summed, not concatenated");
     cfg.load(config_path);
     seed = opt.has_seed ? opt.seed : (uint64_t)cfg.num["seed"];
     const int device = opt.device >= 0 ? opt.device : (int)cfg.num["device"];
@@ -1042,6 +1103,7 @@ struct Driver {
       if (opt.write_files) open_sink(out_dir, popus[0], paired, suffix);
       depth_open(out_dir, popus[0]);
       variants_open(out_dir, popus[0]);
+      errors_open(out_dir, popus[0]);
       set_read_counts(popus[0], reads);
       for (const std::string& chr : genome.chromosomes) run_batch(popus[0], chr, sink);
     } else {
@@ -1057,9 +1119,11 @@ struct Driver {
         drain_wait();  // the previous mixture's last batch still writes into the files about to be closed
         depth_close();
         variants_close();
+        errors_close();
         if (opt.write_files) open_sink(out_dir, stem, paired, suffix);
         depth_open(out_dir, stem);
         variants_open(out_dir, stem);
+        errors_open(out_dir, stem);
         for (size_t i = 0; i < popus.size(); i++) {
           const long popu_reads = (long)(reads * props[i] * acn[popus[i]] / w_acn);  // long*float is a float product (Genome.cpp:935)
           set_read_counts(popus[i], popu_reads);
@@ -1070,6 +1134,7 @@ struct Driver {
     drain_wait();
     depth_close();
     variants_close();
+    errors_close();
     sink.close();
     log("\nReads generation done!\n");
     st.t_total = since(t_all);

@@ -43,6 +43,11 @@ typedef struct simu_options {
                            //    records are made and compressed on the device, piece by piece, in FASTQ order); needs the
                            //    device-assembled haplotypes (refused with host_haplotypes).  Sharded runs write parts like the
                            //    FASTQ parts: rank 0's carries the header, the last rank's the BGZF end-of-file block
+  int32_t truth_errors;    // 1: write per mate, cycle and reported quality how many bases were really wrong -- the read against the
+                           //    haplotype bases it was cut from, so a variant allele is no error -- with a substitution matrix and
+                           //    the sequencing indels to <stem>.truth.errors.tsv beside the FASTQ files (sg_errtab_*; the rule:
+                           //    DESIGN.md "True error counts"), summed like truth_depth.  Needs no piece map: works with
+                           //    host_haplotypes too; refused in a sharded run (partial tables would have to be summed)
   int32_t truth_variants;  // 1: write per variant of the variation and SNP files how many reads cover the site and how many
                            //    carry the allele to <stem>.truth.variants.tsv beside the FASTQ files (sg_variants_*; the
                            //    rule: DESIGN.md "True allele counts"), summed like truth_depth.  Needs the device-assembled
@@ -84,6 +89,9 @@ typedef struct simu_stats {
   uint64_t truth_bytes;    // ... bytes of the record stream and of its BGZF members (header and end-of-file block aside)
   uint64_t truth_bgzf_bytes;
   double t_truth;          // sg_truth_bam calls + fetching and writing their members (synchronous, per piece)
+  uint64_t errors_bases;   // truth_errors: read bases paired with an A/C/G/T template base, ...
+  uint64_t errors_subst;   // ... of which the read shows another letter
+  double t_errors;         // sg_errtab_* calls, formatting and writing the table
   uint64_t variant_rows;   // truth_variants: rows of the variant table, ...
   uint64_t variant_dropped;  // ... input rows left out of it (a contig the FASTA does not hold, a position outside it, no length)
   uint64_t variant_hits;   // ... counts of `total` over all rows and stems

@@ -1,6 +1,6 @@
 // sg_api.h -- what the files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
 // sink, reference, haplotypes, window planner), sg_api_train.cpp (profile training, BGZF / BAM input) and
-// sg_api_depth.cpp (true coverage) and sg_api_variants.cpp (true allele counts).  Internal: the
+// sg_api_depth.cpp (true coverage), sg_api_variants.cpp (true allele counts) and sg_api_errors.cpp (true error counts).  Internal: the
 // ABI itself is include/simuscop_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -92,6 +92,15 @@ struct sg_ctx {
     uint64_t n = 0, reads_hit = 0, hits = 0;
   } variants;
   DevBuf var_rows, var_counts;
+  // true error counts (sg_errtab_*, sg_api_errors.cpp): err_table holds the flat table of 64-bit counters (the layout:
+  // sg_truth.h) and behind it the kernel's five 64-bit counters.  Without sg_errtab_begin nothing is kept and nothing
+  // is allocated.
+  struct Errtab {
+    bool on = false;
+    uint32_t cycles = 0, qual_lo = 0, n_qual = 0, L = 0, cus = 0;
+    uint64_t bases = 0, errors = 0, skipped = 0, reads = 0;
+  } errtab;
+  DevBuf err_table;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // device-made sampling plan: window weights per store id (sg_windows_build), the batch table of sg_plan_windows
   std::map<uint32_t, DevBuf> wstore;

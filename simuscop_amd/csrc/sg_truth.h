@@ -184,6 +184,14 @@ __device__ __forceinline__ ReadGeom read_geom(const DevProfile& P, const DevBatc
   return g;
 }
 
+// rec_offset() of sg_kernels.hip: where read t's FASTQ record starts in its mate's text
+__device__ __forceinline__ uint64_t text_offset(const DevBatch& B, uint32_t m, uint32_t t) {
+  const uint32_t blk = t >> 8;
+  const uint64_t* segbase = (const uint64_t*)((const uint8_t*)B.totals + kTotalsSegBase);
+  return segbase[m * 16u + (blk >> B.seg_shift)] + B.blkbase[(size_t)m * ((B.n_slots + 255u) >> 8) + blk] +
+         B.recloc[(size_t)m * B.n_slots + t];
+}
+
 constexpr uint32_t kTruthMaxOps = 256;     // CIGAR operations of one record (more: SG_ERR_OVERFLOW)
 constexpr uint32_t kTruthWaveOps = 2048;   // ... and of the 64 records one wave packs
 
@@ -360,5 +368,74 @@ struct VariantJob {
   unsigned long long* counters;  // [0] reads with a hit, [1] hits, [2] flags: 1 a template whose first piece was not found
 };
 void launch_variants_add(const DevProfile& P, const DevBatch& B, const VariantJob& J, hipStream_t s);
+
+
+// ---- true error counts per cycle and quality (simuReads --truth-errors; kernel: sg_errors.hip) ----
+// One flat table of 64-bit counters (the layout of sg_errtab_counts, simuscop_amd.h), mate 0 / 1:
+//   Q [2][cycles][n_qual][4]  bases, errors, other, inserted of read position `cycle` reported with quality qual_lo + q
+//   S [2][4][5]               template base (A C T G) -> read letter (A C T G N) of the paired bases
+//   I [2][L][2], D [2][L][2]  events, bases of the sequencing insertions behind / deletions at template base j
+struct ErrtabDims { uint32_t cycles, qual_lo, n_qual, L; };
+enum : uint32_t { kErrBases = 0, kErrErrors = 1, kErrOther = 2, kErrInserted = 3 };
+__host__ __device__ inline uint64_t errtab_q(const ErrtabDims& d, uint32_t mate, uint32_t cycle, uint32_t q) {
+  return (((uint64_t)mate * d.cycles + cycle) * d.n_qual + q) * 4u;
+}
+__host__ __device__ inline uint64_t errtab_s(const ErrtabDims& d, uint32_t mate, uint32_t from, uint32_t to) {
+  return 8ull * d.cycles * d.n_qual + mate * 20u + from * 5u + to;
+}
+__host__ __device__ inline uint64_t errtab_indel(const ErrtabDims& d, uint32_t del, uint32_t mate, uint32_t j) {
+  return 8ull * d.cycles * d.n_qual + 40u + (uint64_t)del * 4u * d.L + ((uint64_t)mate * d.L + j) * 2u;
+}
+__host__ __device__ inline uint64_t errtab_cells(const ErrtabDims& d) { return 8ull * d.cycles * d.n_qual + 40u + 8ull * d.L; }
+
+// a chain's base code as the read sees it: complemented for a reverse read (codes of 4 and above are no A/C/G/T)
+__host__ __device__ inline uint32_t errtab_tmpl_code(uint32_t code, bool reverse) { return reverse && code < 4u ? code ^ 2u : code; }
+// the read's letter as a column of S: A0 C1 T2 G3, anything else (N) 4
+__host__ __device__ inline uint32_t errtab_read_code(uint32_t ch) { return ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'T' ? 2u : ch == 'G' ? 3u : 4u; }
+
+// The counting rule (DESIGN.md "True error counts"): how a read's positions lie over its template T'[0 .. L) in read
+// direction, given its events (ev_pack form, read direction, ascending).  The walk hands over runs, in read order:
+//   seg(0, j, r, n)   read bases r .. r + n - 1 pair with T'[j .. j + n - 1]           (n may be 0)
+//   seg(1, j, r, n)   read bases r .. r + n - 1 were inserted behind the base paired with T'[j]
+//   seg(2, j, r, n)   T'[j .. j + n - 1] was deleted in front of read base r (n already clipped to L - j)
+// and returns the read's length, or kErrWalkBad for events no pass makes: more than SG_MAX_EVENTS, one of length 0, one
+// outside the template or in front of where the event before it ends.
+constexpr uint32_t kErrWalkBad = 0xFFFFFFFFu;
+template <class Seg>
+__host__ __device__ inline uint32_t errtab_walk(const uint32_t* events, uint32_t n_events, uint32_t L, Seg seg) {
+  if (n_events > SG_MAX_EVENTS) return kErrWalkBad;
+  uint32_t j = 0, r = 0;
+  for (uint32_t e = 0; e < n_events; e++) {
+    const uint32_t w = events[e], je = w & 0xFFFFu, k = (w >> 16) & 0x7FFFu;
+    if (je < j || je >= L || k == 0u) return kErrWalkBad;
+    if (w >> 31) {
+      const uint32_t kc = k < L - je ? k : L - je;
+      seg(0u, j, r, je - j);
+      r += je - j;
+      seg(2u, je, r, kc);
+      j = je + kc;
+    } else {
+      seg(0u, j, r, je - j + 1u);
+      r += je - j + 1u;
+      seg(1u, je, r, k);
+      r += k;
+      j = je + 1u;
+    }
+  }
+  seg(0u, j, r, L - j);
+  return r + (L - j);
+}
+
+struct ErrtabJob {
+  ErrtabDims d;
+  uint32_t win_cycles;           // cycles one workgroup stages in LDS (a multiple of 64)
+  unsigned long long* table;     // [errtab_cells]
+  unsigned long long* counters;  // [0] paired A/C/G/T bases, [1] errors among them, [2] reads skipped (live, not inside), [3] reads counted,
+                                 // [4] flags: 2 a walk that does not end at the read's length, 4 a read longer than `cycles`,
+                                 //            8 a quality outside the range, 16 a record outside its mate's text
+};
+constexpr uint32_t kErrLdsBudget = 72u * 1024u;   // two workgroups a CU
+uint32_t errtab_win_cycles(const ErrtabDims& d);
+void launch_errtab_add(const DevProfile& P, const DevBatch& B, const ErrtabJob& J, uint32_t n_cus, hipStream_t s);
 
 }  // namespace sg

@@ -25,14 +25,6 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// rec_offset() of sg_kernels.hip: where read t's FASTQ record starts in its mate's text
-__device__ __forceinline__ uint64_t text_offset(const DevBatch& B, uint32_t m, uint32_t t) {
-  const uint32_t blk = t >> 8;
-  const uint64_t* segbase = (const uint64_t*)((const uint8_t*)B.totals + kTotalsSegBase);
-  return segbase[m * 16u + (blk >> B.seg_shift)] + B.blkbase[(size_t)m * ((B.n_slots + 255u) >> 8) + blk] +
-         B.recloc[(size_t)m * B.n_slots + t];
-}
-
 __device__ __forceinline__ uint32_t qname_len(const DevBatch& B, uint32_t hdr) { return hdr - 2u - (B.paired ? 2u : 0u); }
 
 __global__ __launch_bounds__(256) void truth_size_kernel(DevProfile P, DevBatch B, TruthJob J) {
