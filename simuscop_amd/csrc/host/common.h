@@ -1,6 +1,7 @@
 // host/common.h -- small shared helpers of the C++ host side (string handling with the reference's
 // exact semantics, host Philox for the two host-side draw kinds, error type).
 #pragma once
+#include <chrono>
 #include <cstdint>
 #include <sstream>
 #include <stdexcept>
@@ -14,6 +15,12 @@ namespace simu {
 struct Error : std::runtime_error {
   int exit_code;
   Error(const std::string& m, int code = 1) : std::runtime_error(m), exit_code(code) {}
+};
+
+struct Timed {  // adds the time a scope took to one of the stats' timers, however the scope is left
+  double& d;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  ~Timed() { d += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
 // lib/mydefine/MyDefine.cpp:197-209

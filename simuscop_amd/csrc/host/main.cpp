@@ -264,19 +264,9 @@ int main(int argc, char* argv[]) {
       return 1;
     }
   }
-  if (opt.truth_depth && (gpus > 1 || opt.shard_world > 1)) {
-    std::cerr << "Error: --truth-depth cannot be combined with --world or --gpus above 1: the ranks' partial depths would have to be "
-                 "summed, not concatenated" << std::endl;
-    return 1;
-  }
-  if (opt.truth_variants && (gpus > 1 || opt.shard_world > 1)) {
-    std::cerr << "Error: --truth-variants cannot be combined with --world or --gpus above 1: the ranks' partial counts would have to be "
-                 "summed, not concatenated" << std::endl;
-    return 1;
-  }
-  if (opt.truth_errors && (gpus > 1 || opt.shard_world > 1)) {
-    std::cerr << "Error: --truth-errors cannot be combined with --world or --gpus above 1: the ranks' partial tables would have to be "
-                 "summed, not concatenated" << std::endl;
+  const std::string refusal = simu_truth_refusal(opt, gpus > 1 || opt.shard_world > 1, false);   // (before anything is forked)
+  if (!refusal.empty()) {
+    std::cerr << refusal << std::endl;
     return 1;
   }
   if (gpus > 1) {

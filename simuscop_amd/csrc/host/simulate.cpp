@@ -25,8 +25,7 @@
 
 #include "../../../include/simuscop_amd.h"
 #include "genome.h"
-#include "truth_errors.h"
-#include "truth_variants.h"
+#include "truth_outputs.h"
 
 namespace simu {
 
@@ -42,49 +41,6 @@ namespace {
 
 using Clock = std::chrono::steady_clock;
 inline double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
-
-// One contig's bedGraph rows appended to `out` (simu_depth_format, simulate.h); returns the lines, or UINT64_MAX for data
-// that does not describe a contig of `ln` bases.
-uint64_t depth_format(std::string& out, const std::string& name, uint64_t ln, uint64_t bin, const uint64_t* sums, const sg_depth_run* runs,
-                      uint64_t n) {
-  char buf[96];
-  uint64_t rows = 0;
-  if (bin == 1) {
-    if ((ln == 0) != (n == 0) || (n && runs[0].start != 0)) return UINT64_MAX;
-    for (uint64_t i = 0; i < n;) {
-      uint64_t j = i + 1;
-      while (j < n && runs[j].depth == runs[i].depth) j++;   // (the device's runs differ from their neighbours already)
-      for (uint64_t k = i + 1; k <= j && k < n; k++)
-        if (runs[k].start <= runs[k - 1].start || runs[k].start >= ln) return UINT64_MAX;
-      const uint64_t end = j < n ? runs[j].start : ln;
-      const int m = snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\n", (unsigned long long)runs[i].start, (unsigned long long)end,
-                             (unsigned long long)runs[i].depth);
-      out += name;
-      out.append(buf, (size_t)m);
-      rows++;
-      i = j;
-    }
-    return rows;
-  }
-  if (bin < 1 || n != (ln + bin - 1) / bin) return UINT64_MAX;
-  for (uint64_t k = 0; k < n; k++) {
-    const uint64_t a = k * bin, b = std::min(ln, a + bin);
-    const int m = snprintf(buf, sizeof buf, "\t%llu\t%llu\t%.4f\n", (unsigned long long)a, (unsigned long long)b,
-                           (double)sums[k] / (double)(b - a));
-    out += name;
-    out.append(buf, (size_t)m);
-    rows++;
-  }
-  return rows;
-}
-
-struct Engine {  // RAII around sg_ctx, turns status codes into simu::Error
-  sg_ctx* ctx = nullptr;
-  ~Engine() { if (ctx) sg_destroy(ctx); }
-  void check(int rc, const char* what) {
-    if (rc != SG_OK) throw Error(std::string("GPU engine error in ") + what + ": " + sg_last_error(ctx));
-  }
-};
 
 struct Sink {  // FASTQ output: <output>/<stem>_1.fq + _2.fq, or <stem>.fq (Genome.cpp:857-866)
   FILE* f1 = nullptr;
@@ -152,61 +108,31 @@ struct Driver {
   ~Driver() {
     if (pending.active && pending.th.joinable()) pending.th.join();
     if (pending.active && pending.handle && eng.ctx) sg_release_outputs(eng.ctx, pending.handle);
-    if (fd) fclose(fd);
-    if (fv) fclose(fv);
     for (void* b : pinned)
       if (b && eng.ctx) sg_host_free(eng.ctx, b);
   }
   void log(const std::string& s) { if (!opt.quiet) std::cerr << s; }
 
   // ---- --truth-bam ----
-  // The header's references: the FASTA's contigs in file order, each under the first token of its header line as the
-  // file writes it (`chr20` stays `chr20`, although the reads' names and the variant files say `20`), so that the BAM
-  // and the FASTA name a contig alike.  A contig whose key the file holds twice (the same name again, or `chr20` and
-  // `20`): no read comes from the second sequence and SAM wants every SN once, so only the first is listed (fasta.h;
-  // --unique-contigs refuses such a file).
-  std::vector<std::pair<std::string, uint64_t>> truth_refs() const {
-    std::vector<std::string> name(genome.fa.contigs.size());
-    for (const auto& kv : genome.fa.contig_of) {
-      auto w = genome.fa.written.find(kv.first);
-      name[kv.second] = w == genome.fa.written.end() || w->second.empty() ? kv.first : w->second;
-    }
-    std::vector<std::pair<std::string, uint64_t>> out;
-    for (size_t r = 0; r < name.size(); r++)
-      if (!name[r].empty()) out.emplace_back(name[r], genome.fa.contigs[r].length);
-    return out;
-  }
-  // engine contig (row of the table given to sg_reference_commit) -> refID
-  std::vector<int32_t> truth_ref_ids() const {
-    std::vector<std::string> name(genome.fa.contigs.size());
-    for (const auto& kv : genome.fa.contig_of) name[kv.second] = kv.first;
-    std::vector<int32_t> ids;
-    int32_t next = 0;
-    for (size_t r = 0; r < name.size(); r++) {
-      const int32_t id = name[r].empty() ? -1 : next++;
-      const int32_t dev = genome.fa.dev_row.empty() ? (int32_t)r : genome.fa.dev_row[r];
-      if (dev < 0) continue;
-      if ((size_t)dev >= ids.size()) ids.resize((size_t)dev + 1, 0);
-      ids[(size_t)dev] = id < 0 ? 0 : id;
-    }
-    return ids;
-  }
+  // The contigs as the truth outputs number them (made by open(), once the inputs are loaded), and the outputs that are
+  // summed over a stem: one lifecycle for all of them (truth_outputs.h).  Their files close with them on every path.
+  ContigTable contigs;
+  std::unique_ptr<TruthOutputs> truth;
   // magic, header text, reference list (SAMv1 section 4.2) as BGZF members of their own, made by the device compressor
   void write_truth_header(FILE* f) {
     std::string text = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
-    const auto refs = truth_refs();
-    for (const auto& r : refs) text += "@SQ\tSN:" + r.first + "\tLN:" + std::to_string(r.second) + "\n";
+    for (size_t r = 0; r < contigs.name.size(); r++) text += "@SQ\tSN:" + contigs.name[r] + "\tLN:" + std::to_string(contigs.len[r]) + "\n";
     text += "@PG\tID:simuReads\n";
     std::string h("BAM\1", 4);
     auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; i++) h.push_back((char)(v >> (8 * i))); };
     put32((uint32_t)text.size());
     h += text;
-    put32((uint32_t)refs.size());
-    for (const auto& r : refs) {
-      put32((uint32_t)r.first.size() + 1);
-      h += r.first;
+    put32((uint32_t)contigs.name.size());
+    for (size_t r = 0; r < contigs.name.size(); r++) {
+      put32((uint32_t)contigs.name[r].size() + 1);
+      h += contigs.name[r];
       h.push_back('\0');
-      put32((uint32_t)r.second);
+      put32((uint32_t)contigs.len[r]);
     }
     std::vector<uint8_t> gz(h.size() + h.size() / 2 + 1024 * (h.size() / 32768 + 2));
     uint64_t n = 0;
@@ -232,218 +158,6 @@ struct Driver {
     }
     st.t_truth += since(t0);
   }
-  // ---- --truth-depth ----
-  // The depth array lives on the device from the first stem on; every piece adds its reads (depth_piece), a stem's file
-  // is made when the stem closes -- the device's runs or bin sums, contig by contig in the order of truth_refs(), put
-  // into text here (depth_format) -- and the array is zeroed for the next stem.
-  bool depth_begun = false, depth_stem = false;
-  FILE* fd = nullptr;   // <stem>.truth.depth.bedgraph
-  void depth_begin() {
-    if (!opt.truth_depth || depth_begun) return;
-    std::vector<uint64_t> len;
-    for (const auto& r : truth_refs()) len.push_back(r.second);
-    eng.check(sg_depth_begin(eng.ctx, len.data(), (uint32_t)len.size()), "sg_depth_begin");
-    depth_begun = true;
-  }
-  void depth_open(const std::string& dir, const std::string& stem) {
-    if (!opt.truth_depth) return;
-    auto t0 = Clock::now();
-    depth_begin();
-    depth_stem = true;
-    if (opt.write_files) {
-      const std::string a = dir + "/" + stem + ".truth.depth.bedgraph";
-      fd = fopen(a.c_str(), "wb");
-      if (!fd) throw Error("Error: can not open bedGraph file to save the true depth:\n" + a, -1);
-    }
-    st.t_depth += since(t0);
-  }
-  void depth_piece() {
-    auto t0 = Clock::now();
-    uint64_t mb = 0;
-    eng.check(sg_depth_add(eng.ctx, &mb), "sg_depth_add");
-    st.depth_bases += mb;
-    st.t_depth += since(t0);
-  }
-  void depth_close() {
-    if (!depth_stem) return;
-    auto t0 = Clock::now();
-    depth_stem = false;
-    struct Closer { FILE*& f; ~Closer() { if (f) fclose(f); f = nullptr; } } closer{fd};
-    const auto refs = truth_refs();
-    const uint64_t bin = (uint64_t)opt.truth_depth;
-    std::vector<uint64_t> sums;
-    std::vector<sg_depth_run> runs;
-    std::string text;
-    for (size_t c = 0; c < refs.size(); c++) {
-      uint64_t n = 0;
-      text.clear();
-      if (bin == 1) {
-        eng.check(sg_depth_runs(eng.ctx, (uint32_t)c, nullptr, 0, &n), "sg_depth_runs");
-        if (runs.size() < n) runs.resize(n);
-        if (n) eng.check(sg_depth_runs(eng.ctx, (uint32_t)c, runs.data(), n, &n), "sg_depth_runs");
-        st.depth_rows += depth_format(text, refs[c].first, refs[c].second, 1, nullptr, runs.data(), n);
-      } else {
-        eng.check(sg_depth_bins(eng.ctx, (uint32_t)c, bin, nullptr, 0, &n), "sg_depth_bins");
-        if (sums.size() < n) sums.resize(n);
-        if (n) eng.check(sg_depth_bins(eng.ctx, (uint32_t)c, bin, sums.data(), n, &n), "sg_depth_bins");
-        st.depth_rows += depth_format(text, refs[c].first, refs[c].second, bin, sums.data(), nullptr, n);
-      }
-      if (fd && !text.empty() && fwrite(text.data(), 1, text.size(), fd) != text.size())
-        throw Error("Error: short write to the true depth's bedGraph file", -1);
-    }
-    eng.check(sg_depth_reset(eng.ctx), "sg_depth_reset");
-    st.t_depth += since(t0);
-  }
-
-  // ---- --truth-variants ----
-  // The table is built once from the variation and SNP rows of all populations (variants_build) and lives on the device
-  // with its two counters per row from the first stem on; every piece counts its reads (variants_piece), a stem's file
-  // is written when the stem closes and the counters are zeroed for the next stem.
-  VariantTable vtable;
-  bool variants_built = false, variants_begun = false, variants_stem = false;
-  FILE* fv = nullptr;   // <stem>.truth.variants.tsv
-  void variants_build() {
-    if (variants_built) return;
-    variants_built = true;
-    // contig key (the variant files' names) -> BAM refID, as truth_refs() numbers the contigs
-    std::vector<int32_t> id_of_row(genome.fa.contigs.size(), -1);
-    {
-      std::vector<char> named(genome.fa.contigs.size(), 0);
-      for (const auto& kv : genome.fa.contig_of) named[kv.second] = 1;
-      int32_t next = 0;
-      for (size_t r = 0; r < named.size(); r++)
-        if (named[r]) id_of_row[r] = next++;
-    }
-    auto ref_id = [&](const std::string& chr) {
-      const auto it = genome.fa.contig_of.find(chr);
-      return it == genome.fa.contig_of.end() ? -1 : id_of_row[it->second];
-    };
-    std::vector<VariantIn> in;
-    for (size_t q = 0; q < cfg.popu_names.size(); q++) {
-      const std::string& popu = cfg.popu_names[q];
-      auto each = [&](const auto& by_popu, auto make) {
-        const auto it = by_popu.find(popu);
-        if (it == by_popu.end()) return;
-        for (const auto& kv : it->second) {
-          const int32_t id = ref_id(kv.first);
-          for (const auto& v : kv.second) in.push_back(make(v, id));
-        }
-      };
-      each(genome.snvs, [&](const SNV& v, int32_t id) { return VariantIn{'s', id, (int64_t)v.pos, (int32_t)q, std::string(1, v.alt), 0}; });
-      each(genome.inserts, [&](const Insertion& v, int32_t id) { return VariantIn{'i', id, (int64_t)v.pos, (int32_t)q, v.seq, 0}; });
-      each(genome.dels, [&](const Deletion& v, int32_t id) { return VariantIn{'d', id, (int64_t)v.pos, (int32_t)q, std::string(), (int64_t)v.length}; });
-    }
-    for (const auto& kv : genome.snps) {
-      const int32_t id = ref_id(kv.first);
-      for (const SNP& v : kv.second) in.push_back(VariantIn{'p', id, (int64_t)v.pos, -1, std::string(1, v.nucleotide), 0});
-    }
-    std::vector<uint64_t> len;
-    for (const auto& r : truth_refs()) len.push_back(r.second);
-    vtable.build(in, len, cfg.popu_names.size());
-    st.variant_rows = vtable.rows.size();
-    st.variant_dropped = vtable.dropped;
-  }
-  void variants_begin() {
-    if (!opt.truth_variants || variants_begun) return;
-    auto t0 = Clock::now();
-    variants_build();
-    const std::vector<sg_variant> rows = vtable.abi();
-    eng.check(sg_variants_begin(eng.ctx, rows.data(), rows.size()), "sg_variants_begin");
-    variants_begun = true;
-    st.t_variants += since(t0);
-  }
-  void variants_open(const std::string& dir, const std::string& stem) {
-    if (!opt.truth_variants) return;
-    variants_begin();
-    auto t0 = Clock::now();
-    variants_stem = true;
-    if (opt.write_files) {
-      const std::string a = dir + "/" + stem + ".truth.variants.tsv";
-      fv = fopen(a.c_str(), "wb");
-      if (!fv) throw Error("Error: can not open file to save the true allele counts:\n" + a, -1);
-    }
-    st.t_variants += since(t0);
-  }
-  void variants_piece() {
-    auto t0 = Clock::now();
-    uint64_t rh = 0, h = 0;
-    eng.check(sg_variants_add(eng.ctx, &rh, &h), "sg_variants_add");
-    st.variant_hits += h;
-    st.t_variants += since(t0);
-  }
-  void variants_close() {
-    if (!variants_stem) return;
-    auto t0 = Clock::now();
-    variants_stem = false;
-    struct Closer { FILE*& f; ~Closer() { if (f) fclose(f); f = nullptr; } } closer{fv};
-    if (fv) {
-      std::vector<uint32_t> counts(vtable.rows.size() * 2 + 2);
-      uint64_t n = 0;
-      eng.check(sg_variants_counts(eng.ctx, counts.data(), vtable.rows.size(), &n), "sg_variants_counts");
-      std::vector<std::string> names;
-      for (const auto& r : truth_refs()) names.push_back(r.first);
-      const std::string text = vtable.format(names, cfg.popu_names, counts.data());
-      if (fwrite(text.data(), 1, text.size(), fv) != text.size()) throw Error("Error: short write to the true allele counts' file", -1);
-    }
-    eng.check(sg_variants_reset(eng.ctx), "sg_variants_reset");
-    st.t_variants += since(t0);
-  }
-
-  // ---- --truth-errors ----
-  // The table lives on the device from the first stem on; every piece counts its reads (errors_piece), a stem's file is
-  // made of the table when the stem closes (errors_format, truth_errors.h) and the table is zeroed for the next stem.
-  // The reads are compared with their haplotype templates, so no piece map is involved.
-  bool errors_begun = false, errors_stem = false;
-  FILE* fe = nullptr;   // <stem>.truth.errors.tsv
-  sg_errtab_shape errors_shape{};
-  void errors_begin() {
-    if (!opt.truth_errors || errors_begun) return;
-    // cycles: the template plus what SG_MAX_EVENTS insertions of the longest kind can add; qualities: the profile's
-    // alphabet, at least the 21 an N draws from (Profile::predict)
-    const uint32_t L = (uint32_t)prof.read_length, max_ins = prof.ins_cdf.empty() ? 0u : (uint32_t)prof.ins_cdf.size() - 1u;
-    const uint32_t cycles = (uint32_t)std::min<uint64_t>(0xFFFFu, (uint64_t)L + (uint64_t)SG_MAX_EVENTS * max_ins);
-    const uint32_t qual_lo = (uint32_t)std::max(0, prof.min_qual - 33), n_qual = (uint32_t)std::max(prof.n_qual, 21);
-    eng.check(sg_errtab_begin(eng.ctx, cycles, qual_lo, n_qual), "sg_errtab_begin");
-    eng.check(sg_errtab_info(eng.ctx, &errors_shape), "sg_errtab_info");
-    errors_begun = true;
-  }
-  void errors_open(const std::string& dir, const std::string& stem) {
-    if (!opt.truth_errors) return;
-    auto t0 = Clock::now();
-    errors_begin();
-    errors_stem = true;
-    if (opt.write_files) {
-      const std::string a = dir + "/" + stem + ".truth.errors.tsv";
-      fe = fopen(a.c_str(), "wb");
-      if (!fe) throw Error("Error: can not open file to save the true error counts:\n" + a, -1);
-    }
-    st.t_errors += since(t0);
-  }
-  void errors_piece() {
-    auto t0 = Clock::now();
-    uint64_t b = 0, e = 0;
-    eng.check(sg_errtab_add(eng.ctx, &b, &e), "sg_errtab_add");
-    st.errors_bases += b;
-    st.errors_subst += e;
-    st.t_errors += since(t0);
-  }
-  void errors_close() {
-    if (!errors_stem) return;
-    auto t0 = Clock::now();
-    errors_stem = false;
-    struct Closer { FILE*& f; ~Closer() { if (f) fclose(f); f = nullptr; } } closer{fe};
-    if (fe) {
-      std::vector<uint64_t> table(errors_shape.cells);
-      uint64_t n = 0;
-      eng.check(sg_errtab_counts(eng.ctx, table.data(), table.size(), &n), "sg_errtab_counts");
-      const std::string text = errors_format(table.data(), errors_shape.cycles, errors_shape.qual_lo, errors_shape.n_qual, errors_shape.tmpl_len,
-                                             cfg.paired() ? 2u : 1u, nullptr);
-      if (fwrite(text.data(), 1, text.size(), fe) != text.size()) throw Error("Error: short write to the true error counts' file", -1);
-    }
-    eng.check(sg_errtab_reset(eng.ctx), "sg_errtab_reset");
-    st.t_errors += since(t0);
-  }
-
   void open_sink(const std::string& dir, const std::string& stem, bool paired, const std::string& suffix) {
     sink.open(dir, stem, paired, suffix, opt.gzip != 0);
     if (!opt.truth_bam) return;
@@ -455,16 +169,15 @@ struct Driver {
     const std::string key = popu + "\t" + chr;
     if (resident == key) return;
     ChromPlan& plan = genome.plans[popu][chr];
-    auto t_up = Clock::now();
-    struct Acc { double& d; Clock::time_point t; ~Acc() { d += since(t); } } acc{st.t_hap_device, t_up};
+    Timed acc{st.t_hap_device};
     if (genome.device_haps) {
       eng.check(sg_build_haplotypes(eng.ctx, (int32_t)plan.chain_len.size(), plan.chain_len.data(), plan.pieces.data(),
                                     plan.pieces.size(), plan.literals.data(), plan.literals.size(), plan.patches.data(),
                                     plan.patches.size()),
                 "sg_build_haplotypes");
       if (opt.truth_bam || opt.truth_depth || opt.truth_variants) {  // the copy list is the reads' way back to the reference: contig rows -> refIDs of the BAM header
-        const std::vector<int32_t> ref_ids = truth_ref_ids();
-        eng.check(sg_truth_map(eng.ctx, plan.pieces.data(), plan.piece_seg_first.data(), plan.piece_seg_first.size(), ref_ids.data(), (uint32_t)ref_ids.size()),
+        eng.check(sg_truth_map(eng.ctx, plan.pieces.data(), plan.piece_seg_first.data(), plan.piece_seg_first.size(), contigs.id_of_dev.data(),
+                               (uint32_t)contigs.id_of_dev.size()),
                   "sg_truth_map");
       }
     } else {
@@ -822,9 +535,7 @@ struct Driver {
   // the whole shard as one engine batch (step-by-step sessions: bench.py keeps it resident)
   bool prepare_batch(const std::string& popu, const std::string& chr) {
     if (!build_batch(popu, chr)) return false;
-    depth_begin();   // (a session has no stems: its caller adds, reads and resets the depth itself)
-    variants_begin();
-    errors_begin();
+    truth->begin();   // (a session has no stems: its caller adds, reads and resets the outputs itself)
     plan_range(cur.a0, cur.a1);
     return true;
   }
@@ -882,9 +593,7 @@ struct Driver {
     st.reads += paired ? 2 * nf : nf;
     st.fastq_bytes += n1 + n2;
     if (opt.truth_bam) truth_piece(sink);
-    if (opt.truth_depth) depth_piece();
-    if (opt.truth_variants) variants_piece();
-    if (opt.truth_errors) errors_piece();
+    truth->piece();
     if (!(opt.write_files || opt.fetch)) return;
     bool compressed = false;
     if (opt.gzip) {
@@ -1012,25 +721,8 @@ struct Driver {
   void open(const std::string& config_path) {
     t_all = Clock::now();
     auto t0 = Clock::now();
-    if (opt.truth_bam && opt.host_haplotypes)
-      throw Error("Error: --truth-bam needs the haplotypes assembled on the device (their copy lists map the reads back to the "
-                  "reference); it cannot be combined with --host-haplotypes");
-    if (opt.truth_depth < 0) throw Error("Error: --truth-depth needs a bin width of at least 1");
-    if (opt.truth_depth && opt.host_haplotypes)
-      throw Error("Error: --truth-depth needs the haplotypes assembled on the device (their copy lists map the reads back to the "
-                  "reference); it cannot be combined with --host-haplotypes");
-    if (opt.truth_depth && opt.shard_world > 1)
-      throw Error("Error: --truth-depth cannot be combined with --world or --gpus above 1: the ranks' partial depths would have to "
-                  "be summed, not concatenated");
-    if (opt.truth_variants && opt.host_haplotypes)
-      throw Error("Error: --truth-variants needs the haplotypes assembled on the device (their copy lists map the reads back to the "
-                  "reference); it cannot be combined with --host-haplotypes");
-    if (opt.truth_variants && opt.shard_world > 1)
-      throw Error("Error: --truth-variants cannot be combined with --world or --gpus above 1: the ranks' partial counts would have to "
-                  "be summed, not concatenated");
-    if (opt.truth_errors && opt.shard_world > 1)
-      throw Error("Error: --truth-errors cannot be combined with --world or --gpus above 1: the ranks' partial tables would have to "
-                  "be summed, not concatenated");
+    const std::string refusal = simu_truth_refusal(opt, opt.shard_world > 1, true);
+    if (!refusal.empty()) throw Error(refusal);
     cfg.load(config_path);
     seed = opt.has_seed ? opt.seed : (uint64_t)cfg.num["seed"];
     const int device = opt.device >= 0 ? opt.device : (int)cfg.num["device"];
@@ -1066,6 +758,8 @@ struct Driver {
     struct Joiner { std::thread& t; sg_profile_tables*& T; ~Joiner() { if (t.joinable()) t.join(); if (T) sg_profile_tables_free(T); T = nullptr; } } joiner{prof_thread, tables};
     genome.load_data();
     st.t_reference = genome.t_reference;
+    contigs.build(genome.fa);
+    truth.reset(new TruthOutputs(eng, opt, st, contigs, genome, cfg, prof));
     const std::string out_dir = (opt.output_dir && opt.output_dir[0]) ? opt.output_dir : cfg.str["output"];
     if (opt.write_files) {  // `mkdir -p` (src/simuReads.cpp:56-60)
       for (size_t i = 1; i <= out_dir.size(); i++)
@@ -1101,9 +795,7 @@ struct Driver {
     sink.truth_eof_block = !opt.no_eof_block && (opt.shard_world <= 1 || opt.shard_rank == opt.shard_world - 1);
     if (genome.mix_props.empty()) {
       if (opt.write_files) open_sink(out_dir, popus[0], paired, suffix);
-      depth_open(out_dir, popus[0]);
-      variants_open(out_dir, popus[0]);
-      errors_open(out_dir, popus[0]);
+      truth->open(out_dir, popus[0]);
       set_read_counts(popus[0], reads);
       for (const std::string& chr : genome.chromosomes) run_batch(popus[0], chr, sink);
     } else {
@@ -1117,13 +809,9 @@ struct Driver {
           stem += buf;
         }
         drain_wait();  // the previous mixture's last batch still writes into the files about to be closed
-        depth_close();
-        variants_close();
-        errors_close();
+        truth->close();
         if (opt.write_files) open_sink(out_dir, stem, paired, suffix);
-        depth_open(out_dir, stem);
-        variants_open(out_dir, stem);
-        errors_open(out_dir, stem);
+        truth->open(out_dir, stem);
         for (size_t i = 0; i < popus.size(); i++) {
           const long popu_reads = (long)(reads * props[i] * acn[popus[i]] / w_acn);  // long*float is a float product (Genome.cpp:935)
           set_read_counts(popus[i], popu_reads);
@@ -1132,9 +820,7 @@ struct Driver {
       }
     }
     drain_wait();
-    depth_close();
-    variants_close();
-    errors_close();
+    truth->close();
     sink.close();
     log("\nReads generation done!\n");
     st.t_total = since(t_all);
@@ -1149,18 +835,6 @@ extern "C" void simu_default_options(simu_options* o) {
   o->device = -1;
   o->write_files = 1;
   o->shard_world = 1;
-}
-
-extern "C" uint64_t simu_depth_format(const char* name, uint64_t ln, uint64_t bin, const void* data, uint64_t n, char* out, uint64_t cap,
-                                      uint64_t* rows) {
-  if (!name || (n && !data) || bin < 1) return UINT64_MAX;
-  std::string text;
-  const uint64_t r = simu::depth_format(text, name, ln, bin, bin == 1 ? nullptr : (const uint64_t*)data,
-                                        bin == 1 ? (const sg_depth_run*)data : nullptr, n);
-  if (r == UINT64_MAX) return UINT64_MAX;
-  if (rows) *rows = r;
-  if (out && text.size() <= cap) memcpy(out, text.data(), text.size());
-  return text.size();
 }
 
 extern "C" void simu_assign_contigs(const uint64_t* lengths, int32_t n, int32_t world, int32_t* owner_out) {
@@ -1303,8 +977,7 @@ extern "C" int simu_variant_table(simu_session* s, void* rows, uint64_t cap, uin
   return session_guard(err, err_len, [&]() {
     if (!s || !n) throw simu::Error("simu_variant_table: no session");
     if (!s->d.opt.truth_variants) throw simu::Error("simu_variant_table: the session was not opened with truth_variants");
-    s->d.variants_build();
-    const std::vector<sg_variant> a = s->d.vtable.abi();
+    const std::vector<sg_variant> a = s->d.truth->variant_table().abi();
     *n = a.size();
     const uint64_t m = std::min<uint64_t>(cap, a.size());
     if (rows && m) memcpy(rows, a.data(), (size_t)m * sizeof(sg_variant));

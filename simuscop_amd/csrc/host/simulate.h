@@ -162,4 +162,25 @@ uint64_t simu_batch_slots(simu_session* s);  // planned fragment slots of the pr
 
 #ifdef __cplusplus
 }
+
+#include <string>
+// The rules of the truth options, once, for whoever has to refuse a run: the text of the first one `o` breaks, or "".
+// Needs device haplotypes: an output that maps reads back to the reference reads the haplotypes' copy lists.  Cannot
+// be sharded: an output summed over a stem would come out as partial sums, one per rank.  `sharded`: more than one
+// rank will run; `all`: the rules of a value and of the haplotypes too (the command line leaves those to the run).
+inline std::string simu_truth_refusal(const simu_options& o, bool sharded, bool all) {
+  struct Rule { const char* flag; int32_t on; bool is_width, needs_map; const char* partial; };
+  const Rule rules[] = {{"--truth-bam", o.truth_bam, false, true, nullptr}, {"--truth-depth", o.truth_depth, true, true, "depths"},
+                        {"--truth-variants", o.truth_variants, false, true, "counts"}, {"--truth-errors", o.truth_errors, false, false, "tables"}};
+  for (const Rule& r : rules) {
+    if (all && r.is_width && r.on < 0) return std::string("Error: ") + r.flag + " needs a bin width of at least 1";
+    if (all && r.on && r.needs_map && o.host_haplotypes)
+      return std::string("Error: ") + r.flag + " needs the haplotypes assembled on the device (their copy lists map the reads back to the "
+             "reference); it cannot be combined with --host-haplotypes";
+    if (r.on && r.partial && sharded)
+      return std::string("Error: ") + r.flag + " cannot be combined with --world or --gpus above 1: the ranks' partial " + r.partial +
+             " would have to be summed, not concatenated";
+  }
+  return std::string();
+}
 #endif

@@ -304,6 +304,35 @@ static int commit_chains(sg_ctx* ctx, sg_ctx::ChainLayout&& L) {
   return SG_OK;
 }
 
+// ---- truth outputs: the piece map's and the pass's preconditions (sg_api.h) ----
+static int truth_need_map(sg_ctx* ctx, const char* who) {
+  if (!ctx->truth.from_build)
+    return ctx->fail(SG_ERR_INVALID, std::string(who) + ": the chains have no piece map (they were not made by sg_build_haplotypes)");
+  if (!ctx->truth.mapped) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_truth_map first");
+  return SG_OK;
+}
+
+int sg_pass_prelude(sg_ctx* ctx, const char* who, sg::PieceMap* map, bool bam_names) {
+  if (map)
+    if (int rc = truth_need_map(ctx, who)) return rc;
+  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_result first");
+  const sg::DevBatch& B = ctx->B;
+  const uint32_t nm = B.paired ? 2 : 1;
+  if (map && (uint64_t)B.n_slots * nm >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 reads in one pass");
+  if (bam_names && B.prefix_len > 200) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": read names longer than a BAM record holds");
+  if (B.diag)
+    return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": the pass ran under SG_DIAG (a timing ablation: its reads are not those of their rows)");
+  SG_HIP(hipSetDevice(ctx->device));
+  if (map) {
+    const size_t n_chains = ctx->hap.len.size();
+    map->chain_first = ctx->truth.map.as<uint64_t>();
+    map->pieces = (const sg::TruthPiece*)(ctx->truth.map.as<uint8_t>() + sg::truth_map_pieces_at(n_chains));
+    map->n_chains = (uint32_t)n_chains;
+    map->n_reads = B.n_slots * nm;
+  }
+  return SG_OK;
+}
+
 extern "C" {
 
 uint64_t sg_cdf_count_le(double c) { return sg::count_le(c); }
@@ -952,13 +981,6 @@ int sg_truth_align(const sg_truth_piece* pieces, uint64_t n_pieces, uint64_t tmp
   return A.n_ops > cap ? SG_ERR_OVERFLOW : SG_OK;
 }
 
-static int truth_need_map(sg_ctx* ctx, const char* who) {
-  if (!ctx->truth.from_build)
-    return ctx->fail(SG_ERR_INVALID, std::string(who) + ": the chains have no piece map (they were not made by sg_build_haplotypes)");
-  if (!ctx->truth.mapped) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_truth_map first");
-  return SG_OK;
-}
-
 int sg_truth_map(sg_ctx* ctx, const sg_hap_piece* pieces, const uint8_t* seg_first, uint64_t n_pieces, const int32_t* ref_ids,
                  uint32_t n_ref_ids) {
   if (!ctx || (n_pieces && (!pieces || !seg_first))) return SG_ERR_INVALID;
@@ -1013,11 +1035,11 @@ int sg_truth_map(sg_ctx* ctx, const sg_hap_piece* pieces, const uint8_t* seg_fir
   }
   T.mapped = false;   // (a copy that fails half-way leaves no map rather than a mixed one)
   T.valid = false;
-  const size_t first_b = ((n_chains + 1) * 8 + 63) & ~(size_t)63;
-  SG_ENSURE(ctx->truth_map, first_b + dev.size() * sizeof(sg::TruthPiece) + 64);
-  SG_HIP(hipMemcpyAsync(ctx->truth_map.p, chain_first.data(), (n_chains + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  const size_t first_b = sg::truth_map_pieces_at(n_chains);
+  SG_ENSURE(T.map, first_b + dev.size() * sizeof(sg::TruthPiece) + 64);
+  SG_HIP(hipMemcpyAsync(T.map.p, chain_first.data(), (n_chains + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   if (!dev.empty())
-    SG_HIP(hipMemcpyAsync(ctx->truth_map.as<uint8_t>() + first_b, dev.data(), dev.size() * sizeof(sg::TruthPiece), hipMemcpyHostToDevice, ctx->stream));
+    SG_HIP(hipMemcpyAsync(T.map.as<uint8_t>() + first_b, dev.data(), dev.size() * sizeof(sg::TruthPiece), hipMemcpyHostToDevice, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));   // dev is host memory of this frame
   T.sorted.swap(sorted);
   T.chain_first.swap(chain_first);
@@ -1047,36 +1069,22 @@ int sg_truth_reads(sg_ctx* ctx, int mate, uint32_t first_slot, uint32_t n, sg_tr
   if ((uint64_t)first_slot + n > ctx->B.n_slots) return ctx->fail(SG_ERR_INVALID, "sg_truth_reads: slots past the end of the batch");
   if (!n) return SG_OK;
   SG_HIP(hipSetDevice(ctx->device));
-  SG_ENSURE(ctx->truth_rows, (size_t)n * sizeof(sg::TruthReadRow));
-  sg::launch_truth_reads(ctx->P, ctx->B, (uint32_t)mate, first_slot, n, ctx->truth_rows.as<sg::TruthReadRow>(), ctx->stream);
-  SG_HIP(hipGetLastError());
-  SG_HIP(hipMemcpyAsync(out, ctx->truth_rows.p, (size_t)n * sizeof(sg::TruthReadRow), hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  return SG_OK;
+  SG_ENSURE(ctx->truth.rows, (size_t)n * sizeof(sg::TruthReadRow));
+  sg::launch_truth_reads(ctx->P, ctx->B, (uint32_t)mate, first_slot, n, ctx->truth.rows.as<sg::TruthReadRow>(), ctx->stream);
+  return sg_read_back(ctx, out, ctx->truth.rows.p, (size_t)n * sizeof(sg::TruthReadRow));
 }
 
 int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
   if (!ctx) return SG_ERR_INVALID;
-  if (int rc = truth_need_map(ctx, "sg_truth_bam")) return rc;
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam: call sg_result first");
-  SG_HIP(hipSetDevice(ctx->device));
+  sg::TruthJob J;
+  memset(&J, 0, sizeof J);
+  if (int rc = sg_pass_prelude(ctx, "sg_truth_bam", &J.map, true)) return rc;
   sg_ctx::Truth& T = ctx->truth;
   const sg::DevBatch& B = ctx->B;
-  const uint32_t nm = B.paired ? 2 : 1;
-  if ((uint64_t)B.n_slots * nm >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: more than 2^32 reads in one pass");
-  if (B.prefix_len > 200) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: read names longer than a BAM record holds");
-  if (B.diag) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: the pass ran under SG_DIAG (a timing ablation: its reads are not those of their rows)");
-  const uint32_t N = B.n_slots * nm;
+  const uint32_t N = J.map.n_reads;
   T.valid = false;
   T.rec_bytes = T.gz_bytes = T.records = T.unmapped = 0;
   hipStream_t s = ctx->stream;
-  sg::TruthJob J;
-  memset(&J, 0, sizeof J);
-  const size_t first_b = ((ctx->hap.len.size() + 1) * 8 + 63) & ~(size_t)63;
-  J.chain_first = ctx->truth_map.as<uint64_t>();
-  J.pieces = (const sg::TruthPiece*)(ctx->truth_map.as<uint8_t>() + first_b);
-  J.n_chains = (uint32_t)ctx->hap.len.size();
-  J.n_reads = N;
   // the pack kernel's stages: one record's FASTQ text and one record's image, for reads of up to L + 512 bases
   const uint32_t np_cap = (uint32_t)ctx->P.L + 512u;
   J.text_lds = (16u + 256u + 2u * np_cap + 4u + 31u) & ~15u;
@@ -1086,34 +1094,30 @@ int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
   // work buffer: counters (8 u64: records, unmapped, flags, -, stream bytes) | rows | rec_len | rec_off | block sums
   const size_t off_rows = 64, off_len = off_rows + (size_t)N * sizeof(sg::TruthRow);
   const size_t off_off = (off_len + (size_t)N * 4 + 63) & ~(size_t)63, off_bsum = off_off + (size_t)N * 8;
-  SG_ENSURE(ctx->truth_work, off_bsum + ((size_t)sg::scan_blocks(N) + 8) * 8);
-  uint8_t* wk = ctx->truth_work.as<uint8_t>();
+  SG_ENSURE(T.work, off_bsum + ((size_t)sg::scan_blocks(N) + 8) * 8);
+  uint8_t* wk = T.work.as<uint8_t>();
   J.counters = (unsigned long long*)wk;
   J.rows = (sg::TruthRow*)(wk + off_rows);
   J.rec_len = (uint32_t*)(wk + off_len);
   J.rec_off = (const uint64_t*)(wk + off_off);
-  SG_HIP(hipMemsetAsync(wk, 0, 64, s));
-  uint64_t c[5] = {0, 0, 0, 0, 0};
-  if (N) {
-    sg::launch_truth_size(ctx->P, B, J, s);
-    sg::launch_scan_u32(J.rec_len, N, (uint64_t*)(wk + off_bsum), (uint64_t*)(wk + off_off), (uint64_t*)(wk + 32), s);
-    SG_HIP(hipGetLastError());
-    SG_HIP(hipMemcpyAsync(c, wk, sizeof c, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
-  }
+  uint64_t c[8] = {};
+  if (int rc = sg_run_counted(ctx, wk, 8, c, [&]() {
+        if (!N) return;
+        sg::launch_truth_size(ctx->P, B, J, s);
+        sg::launch_scan_u32(J.rec_len, N, (uint64_t*)(wk + off_bsum), (uint64_t*)(wk + off_off), (uint64_t*)(wk + 32), s);
+      }))
+    return rc;
   if (c[2] & 3) return ctx->fail(SG_ERR_OVERFLOW, "sg_truth_bam: an alignment with more than " + std::to_string(sg::kTruthMaxOps) + " operations");
   const uint64_t total = c[4];
   if (total) {
-    SG_ENSURE(ctx->truth_rec, total + 64);
-    J.out = ctx->truth_rec.as<uint8_t>();
+    SG_ENSURE(T.rec, total + 64);
+    J.out = T.rec.as<uint8_t>();
     J.out_bytes = total;
     sg::launch_truth_pack(ctx->P, B, J, s);
-    SG_HIP(hipGetLastError());
     uint64_t flags = 0;
-    SG_HIP(hipMemcpyAsync(&flags, wk + 16, 8, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
+    if (int rc = sg_read_back(ctx, &flags, wk + 16, 8)) return rc;
     if (flags & 4) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: a record does not fit the record kernel's stages");
-    if (int rc = deflate_text(ctx, ctx->truth_rec.as<uint8_t>(), total, ctx->truth_gz, &T.gz_bytes, "sg_truth_bam")) return rc;
+    if (int rc = deflate_text(ctx, T.rec.as<uint8_t>(), total, T.gz, &T.gz_bytes, "sg_truth_bam")) return rc;
   }
   T.rec_bytes = total;
   T.records = c[0];
@@ -1131,7 +1135,7 @@ int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes,
   if (offset + bytes > (compressed ? ctx->truth.gz_bytes : ctx->truth.rec_bytes)) return ctx->fail(SG_ERR_INVALID, "sg_fetch_truth: range past the end of the data");
   SG_HIP(hipSetDevice(ctx->device));
   if (bytes) {
-    const uint8_t* src = (compressed ? ctx->truth_gz : ctx->truth_rec).as<uint8_t>() + offset;
+    const uint8_t* src = (compressed ? ctx->truth.gz : ctx->truth.rec).as<uint8_t>() + offset;
     SG_HIP(hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipStreamSynchronize(ctx->stream));
   }
@@ -1285,7 +1289,7 @@ int sg_build_haplotypes(sg_ctx* ctx, int32_t n_chains, const uint64_t* lens, con
   sg::launch_hap_copy(ctx->chains.as<uint8_t>(), ctx->ref_codes.as<uint8_t>(), wk + pieces_b + patches_b, (const sg::DevPiece*)wk, dp.size(), ctx->stream);
   sg::launch_hap_patch(ctx->chains.as<uint8_t>(), (const sg::DevPatch*)(wk + pieces_b), pt.size(), ctx->stream);
   const int rc = commit_chains(ctx, std::move(L));   // (synchronises: dp / pt are stack-owned host memory)
-  ctx->truth = sg_ctx::Truth();
+  ctx->truth.forget();
   if (rc == SG_OK) {   // chains with a copy list: sg_truth_map may be given it (nothing of it is kept here)
     ctx->truth.n_given = n_pieces;
     ctx->truth.from_build = true;
@@ -1314,7 +1318,7 @@ int sg_upload_haplotypes(sg_ctx* ctx, int32_t n_chains, const char* const* chain
     if (lens[c]) SG_HIP(hipMemcpyAsync((uint8_t*)ctx->chains.p + L.off[c], chains[c], lens[c], hipMemcpyHostToDevice, ctx->stream));
   // ASCII -> base codes, in place (A0 C1 T2 G3, N=4, other=5): the kernels never see ASCII
   sg::launch_encode((uint8_t*)ctx->chains.p, L.total, ctx->stream);
-  ctx->truth = sg_ctx::Truth();   // strings have no copy list
+  ctx->truth.forget();   // strings have no copy list
   return commit_chains(ctx, std::move(L));
 }
 

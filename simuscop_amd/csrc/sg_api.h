@@ -61,46 +61,51 @@ struct sg_ctx {
   } hap;
   uint64_t gz_bytes[2] = {0, 0};
   bool gz_valid = false;
+  // Each truth output's state owns its device buffers: ending one is assigning a fresh state over it.
   // truth alignments (sg_truth_*): whether the chains came from a copy list (sg_build_haplotypes; how many pieces it
   // had) and, once sg_truth_map has been given that list, its pieces sorted by (chain, dst) with the chains' first
-  // indexes -- on the host for sg_truth_pieces, on the device (truth_map: chain_first, then sg::TruthPiece rows) for the
-  // record kernels.  Without sg_truth_map nothing is kept and nothing is allocated.
-  struct Truth {
+  // indexes -- on the host for sg_truth_pieces, on the device (`map`, laid out as sg::PieceMap says) for the record
+  // kernels.  Without sg_truth_map nothing is kept and nothing is allocated.  New chains forget the map and keep the
+  // buffers (forget).
+  struct TruthInfo {
     uint64_t n_given = 0;
     bool from_build = false, mapped = false, valid = false;
     std::vector<sg_truth_piece> sorted;
     std::vector<uint64_t> chain_first;
     uint64_t rec_bytes = 0, gz_bytes = 0, records = 0, unmapped = 0;
+  };
+  struct Truth : TruthInfo {
+    DevBuf map, work, rec, gz, rows;
+    void forget() { static_cast<TruthInfo&>(*this) = TruthInfo(); }
   } truth;
-  DevBuf truth_map, truth_work, truth_rec, truth_gz, truth_rows;
-  // true coverage (sg_depth_*, sg_api_depth.cpp): the contigs' lengths and first slots in depth_diff, the flat int32
-  // difference array (depth_meta holds both tables for the kernels); depth_work holds one contig's tile sums, run-start
-  // counts and their scans (`scanned` says whose, until the array changes), depth_out a call's bins, rows or depths and
+  // true coverage (sg_depth_*, sg_api_depth.cpp): the contigs' lengths and first slots in `diff`, the flat int32
+  // difference array (`meta` holds both tables for the kernels); `work` holds one contig's tile sums, run-start
+  // counts and their scans (`scanned` says whose, until the array changes), `out` a call's bins, rows or depths and
   // the spans of sg_depth_add_spans.  Without sg_depth_begin nothing is kept and nothing is allocated.
   struct Depth {
     bool on = false;
     std::vector<uint64_t> len, off;
     uint64_t slots = 0, m_bases = 0, scanned_starts = 0;
     int64_t scanned = -1;
+    DevBuf diff, meta, work, out;
   } depth;
-  DevBuf depth_diff, depth_meta, depth_work, depth_out;
-  // true allele counts (sg_variants_*, sg_api_variants.cpp): var_rows holds the sorted table as sg::VariantRow rows,
-  // var_counts the [n][2] uint32 counters (total, alt) and behind them the kernel's three 64-bit counters.  Without
+  // true allele counts (sg_variants_*, sg_api_variants.cpp): `rows` holds the sorted table as sg::VariantRow rows,
+  // `counts` the [n][2] uint32 counters (total, alt) and behind them the kernel's three 64-bit counters.  Without
   // sg_variants_begin nothing is kept and nothing is allocated.
   struct Variants {
     bool on = false;
     uint64_t n = 0, reads_hit = 0, hits = 0;
+    DevBuf rows, counts;
   } variants;
-  DevBuf var_rows, var_counts;
-  // true error counts (sg_errtab_*, sg_api_errors.cpp): err_table holds the flat table of 64-bit counters (the layout:
+  // true error counts (sg_errtab_*, sg_api_errors.cpp): `table` holds the flat table of 64-bit counters (the layout:
   // sg_truth.h) and behind it the kernel's five 64-bit counters.  Without sg_errtab_begin nothing is kept and nothing
   // is allocated.
   struct Errtab {
     bool on = false;
     uint32_t cycles = 0, qual_lo = 0, n_qual = 0, L = 0, cus = 0;
     uint64_t bases = 0, errors = 0, skipped = 0, reads = 0;
+    DevBuf table;
   } errtab;
-  DevBuf err_table;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // device-made sampling plan: window weights per store id (sg_windows_build), the batch table of sg_plan_windows
   std::map<uint32_t, DevBuf> wstore;
@@ -151,3 +156,32 @@ struct sg_ctx {
     int _e = (buf).ensure(bytes);                                                              \
     if (_e) return ctx->hipfail((hipError_t)_e, "hipMalloc(" #buf ")");                        \
   } while (0)
+
+// ---- what the truth outputs' entry points share (sg_truth_bam, sg_depth_*, sg_variants_*, sg_errtab_*) ----
+namespace sg { struct PieceMap; }
+// The start of a call that reads the pass just sampled, with today's checks in today's order: with `map`, the chains'
+// piece map (sg_build_haplotypes, then sg_truth_map); sg_result; with `map`, fewer than 2^32 reads; with `bam_names`, read
+// names that a BAM record holds (sg_truth_bam's own check, whose place is in front of the next); no SG_DIAG.  Then the
+// device is selected and *map filled.  Defined in sg_api.cpp.
+int sg_pass_prelude(sg_ctx* ctx, const char* who, sg::PieceMap* map, bool bam_names = false);
+// no context, or a call in front of its output's X_begin
+inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
+  if (!ctx) return SG_ERR_INVALID;
+  return on ? SG_OK : ctx->fail(SG_ERR_INVALID, std::string(who) + ": call " + begin + " first");
+}
+// Where the 64-bit counters of a counting kernel live: behind `bytes` of cells, 64-byte aligned, with 64 bytes of their own.
+inline size_t sg_counters_at(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+// What the kernels just launched left at `src`, on the host when this returns SG_OK (a failed launch shows here).
+inline int sg_read_back(sg_ctx* ctx, void* dst, const void* src, size_t bytes) {
+  SG_HIP(hipGetLastError());
+  SG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  return SG_OK;
+}
+// Zero n (<= 8) counters, launch, read them back.
+template <class Launch>
+int sg_run_counted(sg_ctx* ctx, void* counters, size_t n, uint64_t* out, Launch launch) {
+  SG_HIP(hipMemsetAsync(counters, 0, n * 8, ctx->stream));
+  launch();
+  return sg_read_back(ctx, out, counters, n * 8);
+}

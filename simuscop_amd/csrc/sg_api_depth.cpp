@@ -1,5 +1,5 @@
 // sg_api_depth.cpp -- the C ABI of the true coverage (sg_depth_*; kernels: sg_depth.hip; the alignment rule: sg_truth.h).
-// The state is sg_ctx::Depth and four buffers of the context; nothing of it exists before sg_depth_begin.
+// The state is sg_ctx::Depth with its four buffers; nothing of it exists before sg_depth_begin.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,27 +15,24 @@ static_assert(sizeof(sg_depth_run) == sizeof(sg::DepthRun), "sg_depth_run is the
 
 namespace {
 
-int depth_need(sg_ctx* ctx, const char* who) {
-  if (!ctx->depth.on) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_depth_begin first");
-  return SG_OK;
-}
+int depth_need(sg_ctx* ctx, const char* who) { return sg_need_begun(ctx, ctx && ctx->depth.on, who, "sg_depth_begin"); }
 int depth_contig(sg_ctx* ctx, const char* who, uint32_t contig) {
   if (int rc = depth_need(ctx, who)) return rc;
   if (contig >= ctx->depth.len.size()) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": contig index out of range");
   return SG_OK;
 }
-// depth_meta: contig_off[n] | contig_len[n] | counters (2 x u64, 64-byte aligned)
-size_t meta_counters(size_t n) { return (2 * n * 8 + 63) & ~(size_t)63; }
+// Depth::meta: contig_off[n] | contig_len[n] | counters (2 x u64)
+size_t meta_counters(size_t n) { return sg_counters_at(2 * n * 8); }
 
 sg::DepthJob depth_job(sg_ctx* ctx) {
   sg::DepthJob J;
   memset(&J, 0, sizeof J);
   const size_t n = ctx->depth.len.size();
-  J.diff = ctx->depth_diff.as<int32_t>();
-  J.contig_off = ctx->depth_meta.as<uint64_t>();
+  J.diff = ctx->depth.diff.as<int32_t>();
+  J.contig_off = ctx->depth.meta.as<uint64_t>();
   J.contig_len = J.contig_off + n;
   J.n_contigs = (uint32_t)n;
-  J.counters = (unsigned long long*)(ctx->depth_meta.as<uint8_t>() + meta_counters(n));
+  J.counters = (unsigned long long*)(ctx->depth.meta.as<uint8_t>() + meta_counters(n));
   J.stage_runs = sg::kDepthStageRuns;
   if (const char* e = getenv("SG_DEPTH_STAGE")) J.stage_runs = std::min(J.stage_runs, (uint32_t)strtoul(e, nullptr, 10));   // (tests: reads that walk twice)
   return J;
@@ -43,13 +40,13 @@ sg::DepthJob depth_job(sg_ctx* ctx) {
 
 sg::DepthView depth_view(sg_ctx* ctx, uint32_t contig) {
   sg::DepthView V;
-  V.diff = ctx->depth_diff.as<int32_t>() + ctx->depth.off[contig];
+  V.diff = ctx->depth.diff.as<int32_t>() + ctx->depth.off[contig];
   V.len = (uint32_t)ctx->depth.len[contig];
   V.n_tiles = (V.len + sg::kDepthTile - 1) / sg::kDepthTile;
   return V;
 }
 
-// depth_work for a contig of n tiles: tile_sum[n] u32 | tile_starts[n] u32 | tile_base[n] u64 | start_base[n] u64 |
+// Depth::work for a contig of n tiles: tile_sum[n] u32 | tile_starts[n] u32 | tile_base[n] u64 | start_base[n] u64 |
 // block sums of the two scans | their totals
 struct WorkLayout {
   size_t sum, starts, base, sbase, bs0, bs1, tot, bytes;
@@ -66,7 +63,7 @@ struct WorkLayout {
   }
 };
 
-// the first half of the finishing pass: tile sums, run-start counts and their scans of `contig` into depth_work
+// the first half of the finishing pass: tile sums, run-start counts and their scans of `contig` into Depth::work
 int depth_scan(sg_ctx* ctx, uint32_t contig) {
   sg_ctx::Depth& D = ctx->depth;
   if (D.scanned == (int64_t)contig) return SG_OK;
@@ -75,29 +72,27 @@ int depth_scan(sg_ctx* ctx, uint32_t contig) {
   const sg::DepthView V = depth_view(ctx, contig);
   if (V.n_tiles) {
     const WorkLayout W(V.n_tiles);
-    SG_ENSURE(ctx->depth_work, W.bytes);
-    uint8_t* wk = ctx->depth_work.as<uint8_t>();
+    SG_ENSURE(ctx->depth.work, W.bytes);
+    uint8_t* wk = ctx->depth.work.as<uint8_t>();
     hipStream_t s = ctx->stream;
     SG_HIP(hipMemsetAsync(wk + W.tot, 0, 64, s));
     sg::launch_depth_tiles(V, (uint32_t*)(wk + W.sum), (uint32_t*)(wk + W.starts), s);
     sg::launch_scan_u32((const uint32_t*)(wk + W.sum), V.n_tiles, (uint64_t*)(wk + W.bs0), (uint64_t*)(wk + W.base), (uint64_t*)(wk + W.tot), s);
     sg::launch_scan_u32((const uint32_t*)(wk + W.starts), V.n_tiles, (uint64_t*)(wk + W.bs1), (uint64_t*)(wk + W.sbase), (uint64_t*)(wk + W.tot + 8), s);
-    SG_HIP(hipGetLastError());
     uint64_t tot[2] = {0, 0};
-    SG_HIP(hipMemcpyAsync(tot, wk + W.tot, sizeof tot, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
+    if (int rc = sg_read_back(ctx, tot, wk + W.tot, sizeof tot)) return rc;
     D.scanned_starts = tot[1];
   }
   D.scanned = (int64_t)contig;
   return SG_OK;
 }
 
-// the counters of a kernel that added: the M bases to the state, the flags to an error
-int depth_added(sg_ctx* ctx, const char* who, const sg::DepthJob& J, uint64_t* m_bases) {
+// a kernel that adds, and its counters: the M bases to the state, the flags to an error
+template <class Launch>
+int depth_added(sg_ctx* ctx, const char* who, const sg::DepthJob& J, uint64_t* m_bases, Launch launch) {
   uint64_t c[2] = {0, 0};
-  SG_HIP(hipGetLastError());
-  SG_HIP(hipMemcpyAsync(c, J.counters, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
-  SG_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->depth.scanned = -1;
+  if (int rc = sg_run_counted(ctx, J.counters, 2, c, launch)) return rc;
   ctx->depth.m_bases += c[0];
   if (m_bases) *m_bases = c[0];
   if (c[1] & 1) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": an alignment lies outside its contig (it was not added)");
@@ -122,19 +117,19 @@ int sg_depth_begin(sg_ctx* ctx, const uint64_t* contig_len, uint32_t n_contigs) 
   sg_ctx::Depth& D = ctx->depth;
   D = sg_ctx::Depth();
   const size_t bytes = (size_t)slots * 4 + 64;
-  if (ctx->depth_diff.ensure(bytes)) {
+  if (ctx->depth.diff.ensure(bytes)) {
     (void)hipGetLastError();
     return ctx->fail(SG_ERR_HIP, "sg_depth_begin: the device cannot hold the difference array of " + std::to_string(bytes) +
                                      " bytes (4 bytes per reference base)");
   }
   const size_t cnt = meta_counters(n_contigs);
-  SG_ENSURE(ctx->depth_meta, cnt + 64);
+  SG_ENSURE(ctx->depth.meta, cnt + 64);
   hipStream_t s = ctx->stream;
-  SG_HIP(hipMemsetAsync(ctx->depth_diff.p, 0, bytes, s));
-  SG_HIP(hipMemsetAsync(ctx->depth_meta.p, 0, cnt + 64, s));
+  SG_HIP(hipMemsetAsync(ctx->depth.diff.p, 0, bytes, s));
+  SG_HIP(hipMemsetAsync(ctx->depth.meta.p, 0, cnt + 64, s));
   if (n_contigs) {
-    SG_HIP(hipMemcpyAsync(ctx->depth_meta.p, off.data(), (size_t)n_contigs * 8, hipMemcpyHostToDevice, s));
-    SG_HIP(hipMemcpyAsync(ctx->depth_meta.as<uint64_t>() + n_contigs, len.data(), (size_t)n_contigs * 8, hipMemcpyHostToDevice, s));
+    SG_HIP(hipMemcpyAsync(ctx->depth.meta.p, off.data(), (size_t)n_contigs * 8, hipMemcpyHostToDevice, s));
+    SG_HIP(hipMemcpyAsync(ctx->depth.meta.as<uint64_t>() + n_contigs, len.data(), (size_t)n_contigs * 8, hipMemcpyHostToDevice, s));
   }
   SG_HIP(hipStreamSynchronize(s));   // len and off are host memory of this frame
   D.len.swap(len);
@@ -145,27 +140,10 @@ int sg_depth_begin(sg_ctx* ctx, const uint64_t* contig_len, uint32_t n_contigs) 
 }
 
 int sg_depth_add(sg_ctx* ctx, uint64_t* m_bases) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = depth_need(ctx, "sg_depth_add")) return rc;
-  if (!ctx->truth.from_build)
-    return ctx->fail(SG_ERR_INVALID, "sg_depth_add: the chains have no piece map (they were not made by sg_build_haplotypes)");
-  if (!ctx->truth.mapped) return ctx->fail(SG_ERR_INVALID, "sg_depth_add: call sg_truth_map first");
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_depth_add: call sg_result first");
-  const sg::DevBatch& B = ctx->B;
-  const uint32_t nm = B.paired ? 2 : 1;
-  if ((uint64_t)B.n_slots * nm >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_depth_add: more than 2^32 reads in one pass");
-  if (B.diag) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_depth_add: the pass ran under SG_DIAG (a timing ablation: its reads are not those of their rows)");
-  SG_HIP(hipSetDevice(ctx->device));
   sg::DepthJob J = depth_job(ctx);
-  const size_t first_b = ((ctx->hap.len.size() + 1) * 8 + 63) & ~(size_t)63;   // the layout of sg_truth_map
-  J.chain_first = ctx->truth_map.as<uint64_t>();
-  J.pieces = (const sg::TruthPiece*)(ctx->truth_map.as<uint8_t>() + first_b);
-  J.n_chains = (uint32_t)ctx->hap.len.size();
-  J.n_reads = B.n_slots * nm;
-  ctx->depth.scanned = -1;
-  SG_HIP(hipMemsetAsync(J.counters, 0, 16, ctx->stream));
-  sg::launch_depth_add(ctx->P, B, J, ctx->stream);
-  return depth_added(ctx, "sg_depth_add", J, m_bases);
+  if (int rc = sg_pass_prelude(ctx, "sg_depth_add", &J.map)) return rc;
+  return depth_added(ctx, "sg_depth_add", J, m_bases, [&]() { sg::launch_depth_add(ctx->P, ctx->B, J, ctx->stream); });
 }
 
 int sg_depth_add_spans(sg_ctx* ctx, const uint32_t* contig, const uint64_t* start, const uint64_t* end, uint64_t n) {
@@ -180,17 +158,16 @@ int sg_depth_add_spans(sg_ctx* ctx, const uint32_t* contig, const uint64_t* star
   if (!n) return SG_OK;
   SG_HIP(hipSetDevice(ctx->device));
   const size_t o_start = ((size_t)n * 4 + 63) & ~(size_t)63, o_end = o_start + (size_t)n * 8;
-  SG_ENSURE(ctx->depth_out, o_end + (size_t)n * 8);
-  uint8_t* buf = ctx->depth_out.as<uint8_t>();
+  SG_ENSURE(ctx->depth.out, o_end + (size_t)n * 8);
+  uint8_t* buf = ctx->depth.out.as<uint8_t>();
   hipStream_t s = ctx->stream;
   SG_HIP(hipMemcpyAsync(buf, contig, (size_t)n * 4, hipMemcpyHostToDevice, s));
   SG_HIP(hipMemcpyAsync(buf + o_start, start, (size_t)n * 8, hipMemcpyHostToDevice, s));
   SG_HIP(hipMemcpyAsync(buf + o_end, end, (size_t)n * 8, hipMemcpyHostToDevice, s));
   const sg::DepthJob J = depth_job(ctx);
-  ctx->depth.scanned = -1;
-  SG_HIP(hipMemsetAsync(J.counters, 0, 16, s));
-  sg::launch_depth_spans(J, (const uint32_t*)buf, (const uint64_t*)(buf + o_start), (const uint64_t*)(buf + o_end), n, s);
-  return depth_added(ctx, "sg_depth_add_spans", J, nullptr);   // (synchronises: the caller's arrays are free again)
+  return depth_added(ctx, "sg_depth_add_spans", J, nullptr, [&]() {   // (synchronises: the caller's arrays are free again)
+    sg::launch_depth_spans(J, (const uint32_t*)buf, (const uint64_t*)(buf + o_start), (const uint64_t*)(buf + o_end), n, s);
+  });
 }
 
 int sg_depth_bins(sg_ctx* ctx, uint32_t contig, uint64_t bin, uint64_t* sums, uint64_t cap, uint64_t* n) {
@@ -204,17 +181,14 @@ int sg_depth_bins(sg_ctx* ctx, uint32_t contig, uint64_t bin, uint64_t* sums, ui
   if (n_bins > cap) return ctx->fail(SG_ERR_OVERFLOW, "sg_depth_bins: the bins do not fit cap");
   SG_HIP(hipSetDevice(ctx->device));
   if (int rc = depth_scan(ctx, contig)) return rc;
-  SG_ENSURE(ctx->depth_out, (size_t)n_bins * 8);
+  SG_ENSURE(ctx->depth.out, (size_t)n_bins * 8);
   hipStream_t s = ctx->stream;
-  SG_HIP(hipMemsetAsync(ctx->depth_out.p, 0, (size_t)n_bins * 8, s));
+  SG_HIP(hipMemsetAsync(ctx->depth.out.p, 0, (size_t)n_bins * 8, s));
   const sg::DepthView V = depth_view(ctx, contig);
   const WorkLayout W(V.n_tiles);
-  sg::launch_depth_bins(V, (const uint64_t*)(ctx->depth_work.as<uint8_t>() + W.base), (uint32_t)std::min<uint64_t>(bin, 0xFFFFFFFFull),
-                        ctx->depth_out.as<unsigned long long>(), s);
-  SG_HIP(hipGetLastError());
-  SG_HIP(hipMemcpyAsync(sums, ctx->depth_out.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s));
-  SG_HIP(hipStreamSynchronize(s));
-  return SG_OK;
+  sg::launch_depth_bins(V, (const uint64_t*)(ctx->depth.work.as<uint8_t>() + W.base), (uint32_t)std::min<uint64_t>(bin, 0xFFFFFFFFull),
+                        ctx->depth.out.as<unsigned long long>(), s);
+  return sg_read_back(ctx, sums, ctx->depth.out.p, (size_t)n_bins * 8);
 }
 
 int sg_depth_runs(sg_ctx* ctx, uint32_t contig, sg_depth_run* rows, uint64_t cap, uint64_t* n) {
@@ -226,16 +200,13 @@ int sg_depth_runs(sg_ctx* ctx, uint32_t contig, sg_depth_run* rows, uint64_t cap
   *n = n_rows;
   if (!cap || !n_rows) return SG_OK;
   if (n_rows > cap) return ctx->fail(SG_ERR_OVERFLOW, "sg_depth_runs: the rows do not fit cap");
-  SG_ENSURE(ctx->depth_out, (size_t)n_rows * sizeof(sg::DepthRun));
+  SG_ENSURE(ctx->depth.out, (size_t)n_rows * sizeof(sg::DepthRun));
   hipStream_t s = ctx->stream;
   const sg::DepthView V = depth_view(ctx, contig);
   const WorkLayout W(V.n_tiles);
-  const uint8_t* wk = ctx->depth_work.as<uint8_t>();
-  sg::launch_depth_runs(V, (const uint64_t*)(wk + W.base), (const uint64_t*)(wk + W.sbase), ctx->depth_out.as<sg::DepthRun>(), n_rows, s);
-  SG_HIP(hipGetLastError());
-  SG_HIP(hipMemcpyAsync(rows, ctx->depth_out.p, (size_t)n_rows * sizeof(sg::DepthRun), hipMemcpyDeviceToHost, s));
-  SG_HIP(hipStreamSynchronize(s));
-  return SG_OK;
+  const uint8_t* wk = ctx->depth.work.as<uint8_t>();
+  sg::launch_depth_runs(V, (const uint64_t*)(wk + W.base), (const uint64_t*)(wk + W.sbase), ctx->depth.out.as<sg::DepthRun>(), n_rows, s);
+  return sg_read_back(ctx, rows, ctx->depth.out.p, (size_t)n_rows * sizeof(sg::DepthRun));
 }
 
 int sg_depth_fetch(sg_ctx* ctx, uint32_t contig, uint64_t first, uint64_t n, uint32_t* depth) {
@@ -246,29 +217,24 @@ int sg_depth_fetch(sg_ctx* ctx, uint32_t contig, uint64_t first, uint64_t n, uin
   if (!n) return SG_OK;
   SG_HIP(hipSetDevice(ctx->device));
   if (int rc = depth_scan(ctx, contig)) return rc;
-  SG_ENSURE(ctx->depth_out, (size_t)n * 4);
+  SG_ENSURE(ctx->depth.out, (size_t)n * 4);
   hipStream_t s = ctx->stream;
   const sg::DepthView V = depth_view(ctx, contig);
   const WorkLayout W(V.n_tiles);
-  sg::launch_depth_fetch(V, (const uint64_t*)(ctx->depth_work.as<uint8_t>() + W.base), (uint32_t)first, (uint32_t)n, ctx->depth_out.as<uint32_t>(), s);
-  SG_HIP(hipGetLastError());
-  SG_HIP(hipMemcpyAsync(depth, ctx->depth_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  SG_HIP(hipStreamSynchronize(s));
-  return SG_OK;
+  sg::launch_depth_fetch(V, (const uint64_t*)(ctx->depth.work.as<uint8_t>() + W.base), (uint32_t)first, (uint32_t)n, ctx->depth.out.as<uint32_t>(), s);
+  return sg_read_back(ctx, depth, ctx->depth.out.p, (size_t)n * 4);
 }
 
 int sg_depth_reset(sg_ctx* ctx) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = depth_need(ctx, "sg_depth_reset")) return rc;
   SG_HIP(hipSetDevice(ctx->device));
-  SG_HIP(hipMemsetAsync(ctx->depth_diff.p, 0, (size_t)ctx->depth.slots * 4, ctx->stream));
+  SG_HIP(hipMemsetAsync(ctx->depth.diff.p, 0, (size_t)ctx->depth.slots * 4, ctx->stream));
   ctx->depth.m_bases = 0;
   ctx->depth.scanned = -1;
   return SG_OK;
 }
 
 int sg_depth_info(sg_ctx* ctx, uint32_t* n_contigs, uint64_t* m_bases, uint32_t* tile) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = depth_need(ctx, "sg_depth_info")) return rc;
   if (n_contigs) *n_contigs = (uint32_t)ctx->depth.len.size();
   if (m_bases) *m_bases = ctx->depth.m_bases;
@@ -277,13 +243,8 @@ int sg_depth_info(sg_ctx* ctx, uint32_t* n_contigs, uint64_t* m_bases, uint32_t*
 }
 
 int sg_depth_end(sg_ctx* ctx) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = depth_need(ctx, "sg_depth_end")) return rc;
   ctx->depth = sg_ctx::Depth();
-  ctx->depth_diff.release();
-  ctx->depth_meta.release();
-  ctx->depth_work.release();
-  ctx->depth_out.release();
   return SG_OK;
 }
 

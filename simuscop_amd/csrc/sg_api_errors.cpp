@@ -1,5 +1,5 @@
 // sg_api_errors.cpp -- the C ABI of the true error counts (sg_errtab_*; kernel: sg_errors.hip; the counting rule:
-// errtab_walk, sg_truth.h).  The state is sg_ctx::Errtab and one buffer of the context; nothing of it exists before
+// errtab_walk, sg_truth.h).  The state is sg_ctx::Errtab with its buffer; nothing of it exists before
 // sg_errtab_begin.
 #include <hip/hip_runtime.h>
 
@@ -12,13 +12,10 @@
 
 namespace {
 
-int errtab_need(sg_ctx* ctx, const char* who) {
-  if (!ctx->errtab.on) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_errtab_begin first");
-  return SG_OK;
-}
+int errtab_need(sg_ctx* ctx, const char* who) { return sg_need_begun(ctx, ctx && ctx->errtab.on, who, "sg_errtab_begin"); }
 sg::ErrtabDims dims_of(const sg_ctx::Errtab& E) { return sg::ErrtabDims{E.cycles, E.qual_lo, E.n_qual, E.L}; }
-// err_table: the table's cells | the kernel's counters (5 x u64, 64-byte aligned)
-size_t table_counters(const sg::ErrtabDims& d) { return ((size_t)sg::errtab_cells(d) * 8 + 63) & ~(size_t)63; }
+// Errtab::table: the table's cells | the kernel's counters (5 x u64)
+size_t table_counters(const sg::ErrtabDims& d) { return sg_counters_at((size_t)sg::errtab_cells(d) * 8); }
 
 bool dims_ok(uint32_t cycles, uint32_t qual_lo, uint32_t n_qual, uint32_t L) {
   return L >= 1u && L <= 0xFFFFu && cycles >= L && cycles <= 0xFFFFu && n_qual >= 1u && n_qual <= 128u && qual_lo + n_qual <= 223u;
@@ -40,38 +37,31 @@ int sg_errtab_begin(sg_ctx* ctx, uint32_t cycles, uint32_t qual_lo, uint32_t n_q
   sg_ctx::Errtab E;
   E.cycles = cycles; E.qual_lo = qual_lo; E.n_qual = n_qual; E.L = L; E.cus = (uint32_t)(cus > 0 ? cus : 0);
   const size_t cnt = table_counters(dims_of(E));
-  SG_ENSURE(ctx->err_table, cnt + 64);
-  SG_HIP(hipMemsetAsync(ctx->err_table.p, 0, cnt + 64, ctx->stream));
+  SG_ENSURE(ctx->errtab.table, cnt + 64);
+  SG_HIP(hipMemsetAsync(ctx->errtab.table.p, 0, cnt + 64, ctx->stream));
+  E.table = std::move(ctx->errtab.table);   // (the state changes only once nothing can fail any more)
   E.on = true;
-  ctx->errtab = E;
+  ctx->errtab = std::move(E);
   return SG_OK;
 }
 
 int sg_errtab_add(sg_ctx* ctx, uint64_t* bases, uint64_t* errors) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = errtab_need(ctx, "sg_errtab_add")) return rc;
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_errtab_add: call sg_result first");
+  if (int rc = sg_pass_prelude(ctx, "sg_errtab_add", nullptr)) return rc;   // (the reads meet their templates: no piece map)
   const sg::DevBatch& B = ctx->B;
-  if (B.diag) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_errtab_add: the pass ran under SG_DIAG (a timing ablation: its reads are not those of their rows)");
   sg_ctx::Errtab& E = ctx->errtab;
   if ((uint32_t)ctx->P.L != E.L) return ctx->fail(SG_ERR_INVALID, "sg_errtab_add: the profile's read length is not the one sg_errtab_begin saw");
   if (bases) *bases = 0;
   if (errors) *errors = 0;
   if (!B.n_slots) return SG_OK;
-  SG_HIP(hipSetDevice(ctx->device));
   sg::ErrtabJob J;
   memset(&J, 0, sizeof J);
   J.d = dims_of(E);
   J.win_cycles = sg::errtab_win_cycles(J.d);
-  J.table = ctx->err_table.as<unsigned long long>();
-  J.counters = (unsigned long long*)(ctx->err_table.as<uint8_t>() + table_counters(J.d));
-  hipStream_t s = ctx->stream;
-  SG_HIP(hipMemsetAsync(J.counters, 0, 40, s));
-  sg::launch_errtab_add(ctx->P, B, J, E.cus, s);
-  SG_HIP(hipGetLastError());
+  J.table = ctx->errtab.table.as<unsigned long long>();
+  J.counters = (unsigned long long*)(ctx->errtab.table.as<uint8_t>() + table_counters(J.d));
   uint64_t c[5] = {0, 0, 0, 0, 0};
-  SG_HIP(hipMemcpyAsync(c, J.counters, sizeof c, hipMemcpyDeviceToHost, s));
-  SG_HIP(hipStreamSynchronize(s));
+  if (int rc = sg_run_counted(ctx, J.counters, 5, c, [&]() { sg::launch_errtab_add(ctx->P, B, J, E.cus, ctx->stream); })) return rc;
   // a failed add folds nothing into the sums: the device's table may hold a part of the pass and is undefined until
   // sg_errtab_reset
   if (c[4] & 2) return ctx->fail(SG_ERR_INVALID, "sg_errtab_add: a read's events do not end at the read's length (the read was not counted)");
@@ -95,16 +85,15 @@ int sg_errtab_counts(sg_ctx* ctx, uint64_t* out, uint64_t cap, uint64_t* n) {
   if (!cap) return SG_OK;
   if (cells > cap) return ctx->fail(SG_ERR_OVERFLOW, "sg_errtab_counts: the table does not fit cap");
   SG_HIP(hipSetDevice(ctx->device));
-  SG_HIP(hipMemcpyAsync(out, ctx->err_table.p, (size_t)cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(out, ctx->errtab.table.p, (size_t)cells * 8, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   return SG_OK;
 }
 
 int sg_errtab_reset(sg_ctx* ctx) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = errtab_need(ctx, "sg_errtab_reset")) return rc;
   SG_HIP(hipSetDevice(ctx->device));
-  SG_HIP(hipMemsetAsync(ctx->err_table.p, 0, table_counters(dims_of(ctx->errtab)) + 64, ctx->stream));
+  SG_HIP(hipMemsetAsync(ctx->errtab.table.p, 0, table_counters(dims_of(ctx->errtab)) + 64, ctx->stream));
   ctx->errtab.bases = ctx->errtab.errors = ctx->errtab.skipped = ctx->errtab.reads = 0;
   return SG_OK;
 }
@@ -129,10 +118,8 @@ int sg_errtab_info(sg_ctx* ctx, sg_errtab_shape* out) {
 }
 
 int sg_errtab_end(sg_ctx* ctx) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = errtab_need(ctx, "sg_errtab_end")) return rc;
   ctx->errtab = sg_ctx::Errtab();
-  ctx->err_table.release();
   return SG_OK;
 }
 

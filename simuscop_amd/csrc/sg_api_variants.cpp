@@ -1,5 +1,5 @@
 // sg_api_variants.cpp -- the C ABI of the true allele counts (sg_variants_*, sg_variant_observe; kernel: sg_variants.hip;
-// the counting rule: truth_variant_scan, sg_truth.h).  The state is sg_ctx::Variants and two buffers of the context;
+// the counting rule: truth_variant_scan, sg_truth.h).  The state is sg_ctx::Variants with its two buffers;
 // nothing of it exists before sg_variants_begin.
 #include <hip/hip_runtime.h>
 
@@ -16,12 +16,9 @@ static_assert(sizeof(sg::VariantRow) == 16, "the scan loads a row as 16 bytes");
 
 namespace {
 
-int variants_need(sg_ctx* ctx, const char* who) {
-  if (!ctx->variants.on) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_variants_begin first");
-  return SG_OK;
-}
-// var_counts: counts[n][2] u32 | the kernel's counters (3 x u64, 64-byte aligned)
-size_t counts_counters(uint64_t n) { return ((size_t)n * 8 + 63) & ~(size_t)63; }
+int variants_need(sg_ctx* ctx, const char* who) { return sg_need_begun(ctx, ctx && ctx->variants.on, who, "sg_variants_begin"); }
+// Variants::counts: counts[n][2] u32 | the kernel's counters (3 x u64)
+size_t counts_counters(uint64_t n) { return sg_counters_at((size_t)n * 8); }
 
 // The ABI's rows as the scan's; the index of the first row that breaks the rules, or n.
 uint64_t variant_rows(const sg_variant* rows, uint64_t n, std::vector<sg::VariantRow>& out) {
@@ -53,11 +50,11 @@ int sg_variants_begin(sg_ctx* ctx, const sg_variant* rows, uint64_t n) {
   SG_HIP(hipSetDevice(ctx->device));
   ctx->variants = sg_ctx::Variants();
   const size_t cnt = counts_counters(n);
-  SG_ENSURE(ctx->var_rows, (size_t)n * sizeof(sg::VariantRow) + 64);
-  SG_ENSURE(ctx->var_counts, cnt + 64);
+  SG_ENSURE(ctx->variants.rows, (size_t)n * sizeof(sg::VariantRow) + 64);
+  SG_ENSURE(ctx->variants.counts, cnt + 64);
   hipStream_t s = ctx->stream;
-  SG_HIP(hipMemsetAsync(ctx->var_counts.p, 0, cnt + 64, s));
-  if (n) SG_HIP(hipMemcpyAsync(ctx->var_rows.p, tab.data(), (size_t)n * sizeof(sg::VariantRow), hipMemcpyHostToDevice, s));
+  SG_HIP(hipMemsetAsync(ctx->variants.counts.p, 0, cnt + 64, s));
+  if (n) SG_HIP(hipMemcpyAsync(ctx->variants.rows.p, tab.data(), (size_t)n * sizeof(sg::VariantRow), hipMemcpyHostToDevice, s));
   SG_HIP(hipStreamSynchronize(s));   // tab is host memory of this frame
   ctx->variants.n = n;
   ctx->variants.on = true;
@@ -65,38 +62,19 @@ int sg_variants_begin(sg_ctx* ctx, const sg_variant* rows, uint64_t n) {
 }
 
 int sg_variants_add(sg_ctx* ctx, uint64_t* reads_hit, uint64_t* hits) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = variants_need(ctx, "sg_variants_add")) return rc;
-  if (!ctx->truth.from_build)
-    return ctx->fail(SG_ERR_INVALID, "sg_variants_add: the chains have no piece map (they were not made by sg_build_haplotypes)");
-  if (!ctx->truth.mapped) return ctx->fail(SG_ERR_INVALID, "sg_variants_add: call sg_truth_map first");
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_variants_add: call sg_result first");
-  const sg::DevBatch& B = ctx->B;
-  const uint32_t nm = B.paired ? 2 : 1;
-  if ((uint64_t)B.n_slots * nm >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_variants_add: more than 2^32 reads in one pass");
-  if (B.diag) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_variants_add: the pass ran under SG_DIAG (a timing ablation: its reads are not those of their rows)");
+  sg::VariantJob J;
+  memset(&J, 0, sizeof J);
+  if (int rc = sg_pass_prelude(ctx, "sg_variants_add", &J.map)) return rc;
   if (reads_hit) *reads_hit = 0;
   if (hits) *hits = 0;
   if (!ctx->variants.n) return SG_OK;
-  SG_HIP(hipSetDevice(ctx->device));
-  sg::VariantJob J;
-  memset(&J, 0, sizeof J);
-  const size_t first_b = ((ctx->hap.len.size() + 1) * 8 + 63) & ~(size_t)63;   // the layout of sg_truth_map
-  J.chain_first = ctx->truth_map.as<uint64_t>();
-  J.pieces = (const sg::TruthPiece*)(ctx->truth_map.as<uint8_t>() + first_b);
-  J.n_chains = (uint32_t)ctx->hap.len.size();
-  J.n_reads = B.n_slots * nm;
-  J.table = ctx->var_rows.as<sg::VariantRow>();
+  J.table = ctx->variants.rows.as<sg::VariantRow>();
   J.n_rows = ctx->variants.n;
-  J.counts = ctx->var_counts.as<uint32_t>();
-  J.counters = (unsigned long long*)(ctx->var_counts.as<uint8_t>() + counts_counters(J.n_rows));
-  hipStream_t s = ctx->stream;
-  SG_HIP(hipMemsetAsync(J.counters, 0, 24, s));
-  sg::launch_variants_add(ctx->P, B, J, s);
-  SG_HIP(hipGetLastError());
+  J.counts = ctx->variants.counts.as<uint32_t>();
+  J.counters = (unsigned long long*)(ctx->variants.counts.as<uint8_t>() + counts_counters(J.n_rows));
   uint64_t c[3] = {0, 0, 0};
-  SG_HIP(hipMemcpyAsync(c, J.counters, sizeof c, hipMemcpyDeviceToHost, s));
-  SG_HIP(hipStreamSynchronize(s));
+  if (int rc = sg_run_counted(ctx, J.counters, 3, c, [&]() { sg::launch_variants_add(ctx->P, ctx->B, J, ctx->stream); })) return rc;
   ctx->variants.reads_hit += c[0];
   ctx->variants.hits += c[1];
   if (reads_hit) *reads_hit = c[0];
@@ -113,24 +91,22 @@ int sg_variants_counts(sg_ctx* ctx, uint32_t* out, uint64_t cap, uint64_t* n) {
   if (!cap || !rows) return SG_OK;
   if (rows > cap) return ctx->fail(SG_ERR_OVERFLOW, "sg_variants_counts: the rows do not fit cap");
   SG_HIP(hipSetDevice(ctx->device));
-  SG_HIP(hipMemcpyAsync(out, ctx->var_counts.p, (size_t)rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SG_HIP(hipMemcpyAsync(out, ctx->variants.counts.p, (size_t)rows * 8, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   for (uint64_t i = 0; i < rows; i++) std::swap(out[2 * i], out[2 * i + 1]);   // the device keeps (total, alt)
   return SG_OK;
 }
 
 int sg_variants_reset(sg_ctx* ctx) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = variants_need(ctx, "sg_variants_reset")) return rc;
   SG_HIP(hipSetDevice(ctx->device));
-  SG_HIP(hipMemsetAsync(ctx->var_counts.p, 0, counts_counters(ctx->variants.n) + 64, ctx->stream));
+  SG_HIP(hipMemsetAsync(ctx->variants.counts.p, 0, counts_counters(ctx->variants.n) + 64, ctx->stream));
   ctx->variants.reads_hit = 0;
   ctx->variants.hits = 0;
   return SG_OK;
 }
 
 int sg_variants_info(sg_ctx* ctx, uint64_t* n_rows, uint64_t* reads_hit, uint64_t* hits) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = variants_need(ctx, "sg_variants_info")) return rc;
   if (n_rows) *n_rows = ctx->variants.n;
   if (reads_hit) *reads_hit = ctx->variants.reads_hit;
@@ -139,11 +115,8 @@ int sg_variants_info(sg_ctx* ctx, uint64_t* n_rows, uint64_t* reads_hit, uint64_
 }
 
 int sg_variants_end(sg_ctx* ctx) {
-  if (!ctx) return SG_ERR_INVALID;
   if (int rc = variants_need(ctx, "sg_variants_end")) return rc;
   ctx->variants = sg_ctx::Variants();
-  ctx->var_rows.release();
-  ctx->var_counts.release();
   return SG_OK;
 }
 

@@ -49,21 +49,19 @@ __device__ __forceinline__ void count_and_flag(const DepthJob& J, uint64_t bases
 __global__ __launch_bounds__(kAddThreads) void depth_add_kernel(DevProfile P, DevBatch B, DepthJob J) {
   __shared__ uint32_t st_rel[kStageRuns * kAddThreads], st_len[kStageRuns * kAddThreads];   // [run][lane]: no bank conflict
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t nm = B.paired ? 2u : 1u;
-  const bool in_range = idx < J.n_reads;
-  const uint32_t t = in_range ? idx / nm : 0u, m = in_range ? idx % nm : 0u;
+  const PassRead R = pass_read(B, idx, J.map.n_reads);
   ReadGeom g = {};
-  if (in_range) g = read_geom(P, B, t, m);
+  if (R.in_range) g = read_geom(P, B, R.t, R.m);
   uint64_t bases = 0;
   uint32_t flags = 0;
-  if (g.live && g.inside && g.chain < J.n_chains) {
-    const uint64_t last = J.chain_first[g.chain + 1];
-    const uint64_t pi = truth_find_piece(J.pieces, J.chain_first[g.chain], last, g.tmpl_off);
+  if (g.live && g.inside && g.chain < J.map.n_chains) {
+    const uint64_t last = J.map.chain_first[g.chain + 1];
+    const uint64_t pi = truth_find_piece(J.map.pieces, J.map.chain_first[g.chain], last, g.tmpl_off);
     // `put` is told lengths, not positions, and the alignment's start only comes back with the walk: the M runs are kept
     // as offsets from that start (M, D and N move along the reference).  What the end of the walk withdraws is never M.
     uint32_t n_runs = 0, rel = 0, m_end = 0;
     const uint32_t tid = threadIdx.x;
-    const TruthAln A = truth_walk(J.pieces, last, pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev, [&](uint32_t, uint32_t v) {
+    const TruthAln A = truth_walk(J.map.pieces, last, pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev, [&](uint32_t, uint32_t v) {
       const uint32_t op = v & 15u, len = v >> 4;
       if (op == kOpM) {
         if (n_runs < J.stage_runs) { st_rel[n_runs * kAddThreads + tid] = rel; st_len[n_runs * kAddThreads + tid] = len; }
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(kAddThreads) void depth_add_kernel(DevProfile P, De
         }
       } else {   // more runs than the stage holds: the walk again, now that its start is known
         uint32_t rel2 = 0;
-        truth_walk(J.pieces, last, pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev, [&](uint32_t, uint32_t v) {
+        truth_walk(J.map.pieces, last, pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev, [&](uint32_t, uint32_t v) {
           const uint32_t op = v & 15u, len = v >> 4;
           if (op == kOpM) {
             const uint32_t f = add_run(J, A.contig, A.pos0 + rel2, len);
@@ -271,8 +269,8 @@ __global__ __launch_bounds__(64) void depth_fetch_kernel(DepthView V, const uint
 }  // namespace
 
 void launch_depth_add(const DevProfile& P, const DevBatch& B, const DepthJob& J, hipStream_t s) {
-  if (!J.n_reads) return;
-  hipLaunchKernelGGL(depth_add_kernel, dim3((J.n_reads + kAddThreads - 1u) / kAddThreads), dim3(kAddThreads), 0, s, P, B, J);
+  if (!J.map.n_reads) return;
+  hipLaunchKernelGGL(depth_add_kernel, dim3((J.map.n_reads + kAddThreads - 1u) / kAddThreads), dim3(kAddThreads), 0, s, P, B, J);
 }
 void launch_depth_spans(const DepthJob& J, const uint32_t* contig, const uint64_t* start, const uint64_t* end, uint64_t n, hipStream_t s) {
   if (!n) return;

@@ -202,11 +202,33 @@ struct TruthRow {
   uint32_t n_ops;
 };
 
-struct TruthJob {
+// The piece map as a pass's kernels read it, and the reads they run over: the first member of every job that maps reads
+// back to the reference.  On the device the map is one buffer (sg_truth_map writes it, the pass prelude of sg_api.h
+// reads it): chain_first, then from truth_map_pieces_at() on the pieces.
+struct PieceMap {
   const TruthPiece* pieces;
   const uint64_t* chain_first;   // [n_chains + 1] first piece of every chain
   uint32_t n_chains;
   uint32_t n_reads;              // n_slots * mates
+};
+inline size_t truth_map_pieces_at(size_t n_chains) { return ((n_chains + 1) * 8 + 63) & ~(size_t)63; }
+
+// Read `idx` of a pass in record order (index = slot * mates + mate): whether there is one, its slot and its mate.  The
+// kernels then take its geometry behind `in_range` (an index behind the last read keeps the empty one: not live) and
+// test its chain against the piece map's.  (Those stay the caller's own lines: with the geometry fetched or tested
+// through a wrapper too, the kernels come out with other register counts than they had.)
+struct PassRead {
+  bool in_range;
+  uint32_t t, m;
+};
+__device__ __forceinline__ PassRead pass_read(const DevBatch& B, uint32_t idx, uint32_t n_reads) {
+  const uint32_t nm = B.paired ? 2u : 1u;
+  const bool in_range = idx < n_reads;
+  return PassRead{in_range, in_range ? idx / nm : 0u, in_range ? idx % nm : 0u};
+}
+
+struct TruthJob {
+  PieceMap map;
   TruthRow* rows;                // [n_reads]
   uint32_t* rec_len;             // [n_reads] bytes of the record with its block_size word (0: unused slot)
   const uint64_t* rec_off;       // [n_reads] exclusive scan of rec_len
@@ -234,9 +256,7 @@ void launch_truth_reads(const DevProfile& P, const DevBatch& B, uint32_t mate, u
 constexpr uint32_t kDepthStageRuns = 8; // M runs of a read depth_add_kernel stages in LDS (a read with more walks twice)
 constexpr uint32_t kDepthTile = 4096;   // bases one wave of the finishing pass rebuilds (16 steps of 64 lanes x 4 bases)
 struct DepthJob {
-  const TruthPiece* pieces;
-  const uint64_t* chain_first;
-  uint32_t n_chains, n_reads;
+  PieceMap map;
   int32_t* diff;
   const uint64_t* contig_off;    // [n_contigs] first slot of each contig
   const uint64_t* contig_len;    // [n_contigs]
@@ -359,9 +379,7 @@ __host__ __device__ inline void truth_variant_scan(const TruthPiece* pieces, uin
 }
 
 struct VariantJob {
-  const TruthPiece* pieces;
-  const uint64_t* chain_first;
-  uint32_t n_chains, n_reads;
+  PieceMap map;
   const VariantRow* table;
   uint64_t n_rows;
   uint32_t* counts;              // [n_rows][2]: total, alt

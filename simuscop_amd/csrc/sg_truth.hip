@@ -29,24 +29,22 @@ __device__ __forceinline__ uint32_t qname_len(const DevBatch& B, uint32_t hdr) {
 
 __global__ __launch_bounds__(256) void truth_size_kernel(DevProfile P, DevBatch B, TruthJob J) {
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t nm = B.paired ? 2u : 1u;
-  const bool in_range = idx < J.n_reads;
-  const uint32_t t = in_range ? idx / nm : 0u, m = in_range ? idx % nm : 0u;
+  const PassRead R = pass_read(B, idx, J.map.n_reads);
   ReadGeom g = {};
-  if (in_range) g = read_geom(P, B, t, m);
+  if (R.in_range) g = read_geom(P, B, R.t, R.m);
   TruthRow row = {-1, -1, -1, 0u};
   uint32_t len = 0, flags = 0;
   if (g.live) {
-    if (g.inside && g.chain < J.n_chains) {
-      const uint64_t pi = truth_find_piece(J.pieces, J.chain_first[g.chain], J.chain_first[g.chain + 1], g.tmpl_off);
-      const TruthAln A = truth_walk(J.pieces, J.chain_first[g.chain + 1], pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev,
+    if (g.inside && g.chain < J.map.n_chains) {
+      const uint64_t pi = truth_find_piece(J.map.pieces, J.map.chain_first[g.chain], J.map.chain_first[g.chain + 1], g.tmpl_off);
+      const TruthAln A = truth_walk(J.map.pieces, J.map.chain_first[g.chain + 1], pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev,
                                     [](uint32_t, uint32_t) {});
       if (A.n_ops > kTruthMaxOps) flags |= 1u;
       else if (A.n_ops) row = TruthRow{A.contig, (int32_t)A.pos0, (int32_t)A.end, A.n_ops};
     }
     len = 36u + qname_len(B, g.hdr) + 1u + 4u * row.n_ops + (g.np + 1u) / 2u + g.np;
   }
-  if (in_range) {
+  if (R.in_range) {
     J.rows[idx] = row;
     J.rec_len[idx] = len;
   }
@@ -78,14 +76,14 @@ __global__ __launch_bounds__(64) void truth_pack_kernel(DevProfile P, DevBatch B
   const uint32_t lane = threadIdx.x;
   const uint32_t idx = blockIdx.x * 64u + lane;
   const uint32_t nm = B.paired ? 2u : 1u;
-  const bool in_range = idx < J.n_reads;
-  const uint32_t t = in_range ? idx / nm : 0u, m = in_range ? idx % nm : 0u;
   // ---- phase A: lane = read ----
+  const PassRead R = pass_read(B, idx, J.map.n_reads);
+  const uint32_t t = R.t, m = R.m;
   ReadGeom g = {};
   TruthRow row = {-1, -1, -1, 0u};
   uint32_t rec_len = 0;
   uint64_t rec_off = 0, toff = 0;
-  if (in_range) {
+  if (R.in_range) {
     rec_len = J.rec_len[idx];
     if (rec_len) {
       g = read_geom(P, B, t, m);
@@ -104,10 +102,10 @@ __global__ __launch_bounds__(64) void truth_pack_kernel(DevProfile P, DevBatch B
   cig_base -= row.n_ops;
   const bool mapped = row.n_ops != 0u;
   if (live && mapped && cig_base + row.n_ops <= kTruthWaveOps) {
-    const uint64_t pi = truth_find_piece(J.pieces, J.chain_first[g.chain], J.chain_first[g.chain + 1], g.tmpl_off);
+    const uint64_t pi = truth_find_piece(J.map.pieces, J.map.chain_first[g.chain], J.map.chain_first[g.chain + 1], g.tmpl_off);
     const uint32_t n_ops = row.n_ops;
     uint32_t* const mine = cig + cig_base;
-    truth_walk(J.pieces, J.chain_first[g.chain + 1], pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev,
+    truth_walk(J.map.pieces, J.map.chain_first[g.chain + 1], pi, g.tmpl_off, (uint32_t)P.L, g.reverse != 0u, g.events, g.nev,
                [=](uint32_t i, uint32_t v) { if (i < n_ops) mine[i] = v; });
   }
   if (live) {
@@ -225,14 +223,14 @@ __global__ __launch_bounds__(256) void truth_reads_kernel(DevProfile P, DevBatch
 }  // namespace
 
 void launch_truth_size(const DevProfile& P, const DevBatch& B, const TruthJob& J, hipStream_t s) {
-  if (!J.n_reads) return;
-  hipLaunchKernelGGL(truth_size_kernel, dim3((J.n_reads + 255u) / 256u), dim3(256), 0, s, P, B, J);
+  if (!J.map.n_reads) return;
+  hipLaunchKernelGGL(truth_size_kernel, dim3((J.map.n_reads + 255u) / 256u), dim3(256), 0, s, P, B, J);
 }
 void launch_truth_pack(const DevProfile& P, const DevBatch& B, const TruthJob& J, hipStream_t s) {
-  if (!J.n_reads) return;
+  if (!J.map.n_reads) return;
   const size_t lds = (size_t)kTruthWaveOps * 4 + 64 * 9 * 4 + J.text_lds + J.image_lds;
   (void)hipFuncSetAttribute((const void*)truth_pack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(truth_pack_kernel, dim3((J.n_reads + 63u) / 64u), dim3(64), lds, s, P, B, J);
+  hipLaunchKernelGGL(truth_pack_kernel, dim3((J.map.n_reads + 63u) / 64u), dim3(64), lds, s, P, B, J);
 }
 void launch_truth_reads(const DevProfile& P, const DevBatch& B, uint32_t mate, uint32_t first_slot, uint32_t n, TruthReadRow* out, hipStream_t s) {
   if (!n) return;

@@ -18,20 +18,18 @@ constexpr uint32_t kVarThreads = 256;
 
 __global__ __launch_bounds__(kVarThreads) void variants_add_kernel(DevProfile P, DevBatch B, VariantJob J) {
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t nm = B.paired ? 2u : 1u;
-  const bool in_range = idx < J.n_reads;
-  const uint32_t t = in_range ? idx / nm : 0u, m = in_range ? idx % nm : 0u;
+  const PassRead R = pass_read(B, idx, J.map.n_reads);
   ReadGeom g = {};
-  if (in_range) g = read_geom(P, B, t, m);
+  if (R.in_range) g = read_geom(P, B, R.t, R.m);
   uint32_t hits = 0, flags = 0;
-  if (g.live && g.inside && g.chain < J.n_chains) {
-    const uint64_t first = J.chain_first[g.chain], last = J.chain_first[g.chain + 1];
-    const uint64_t pi = first < last ? truth_find_piece(J.pieces, first, last, g.tmpl_off) : last;
-    if (pi >= last || J.pieces[pi].dst > g.tmpl_off || g.tmpl_off - J.pieces[pi].dst >= J.pieces[pi].len) {
+  if (g.live && g.inside && g.chain < J.map.n_chains) {
+    const uint64_t first = J.map.chain_first[g.chain], last = J.map.chain_first[g.chain + 1];
+    const uint64_t pi = first < last ? truth_find_piece(J.map.pieces, first, last, g.tmpl_off) : last;
+    if (pi >= last || J.map.pieces[pi].dst > g.tmpl_off || g.tmpl_off - J.map.pieces[pi].dst >= J.map.pieces[pi].len) {
       flags = 1u;
     } else {
       const uint8_t* codes = B.chains + B.chain_off[g.chain];
-      truth_variant_scan(J.pieces, last, pi, g.tmpl_off, (uint32_t)P.L, codes, 0, J.table, J.n_rows, [&](uint64_t row, bool alt) {
+      truth_variant_scan(J.map.pieces, last, pi, g.tmpl_off, (uint32_t)P.L, codes, 0, J.table, J.n_rows, [&](uint64_t row, bool alt) {
         atomicAdd(&J.counts[row * 2], 1u);
         if (alt) atomicAdd(&J.counts[row * 2 + 1], 1u);
         hits++;
@@ -54,8 +52,8 @@ __global__ __launch_bounds__(kVarThreads) void variants_add_kernel(DevProfile P,
 }  // namespace
 
 void launch_variants_add(const DevProfile& P, const DevBatch& B, const VariantJob& J, hipStream_t s) {
-  if (!J.n_reads || !J.n_rows) return;
-  hipLaunchKernelGGL(variants_add_kernel, dim3((J.n_reads + kVarThreads - 1u) / kVarThreads), dim3(kVarThreads), 0, s, P, B, J);
+  if (!J.map.n_reads || !J.n_rows) return;
+  hipLaunchKernelGGL(variants_add_kernel, dim3((J.map.n_reads + kVarThreads - 1u) / kVarThreads), dim3(kVarThreads), 0, s, P, B, J);
 }
 
 }  // namespace sg
