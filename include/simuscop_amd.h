@@ -188,13 +188,24 @@ int sg_plan(sg_ctx* ctx, const sg_batch* batch);
  * formatting) for the planned batch.  Results stay in device memory.  A context that already holds
  * output buffers (any pass but its first) queues the pass without waiting for anything: what the
  * pass reports -- SG_ERR_OVERFLOW for a read with more than SG_MAX_EVENTS sequencing indels -- then
- * comes from sg_result / sg_fetch instead.                                                       */
+ * comes from the first of sg_result / sg_fetch / sg_fetch_range / sg_device_output instead; a pass
+ * that failed so is gone (sg_sample runs the plan again).
+ *
+ * New chains (sg_upload_haplotypes, sg_build_haplotypes) or a new profile (sg_load_profile,
+ * sg_load_prepared_profile) end the plan: sg_sample asks for sg_plan again.  A pass already sampled
+ * keeps its text -- sg_result, sg_fetch, sg_fetch_range, sg_device_output, sg_compress,
+ * sg_fetch_compressed, sg_detach_outputs, sg_emit_info and sg_emit_path go on working until the next
+ * sg_plan / sg_sample -- but its rows are no longer those of the chains and the profile: the calls
+ * that read them (sg_truth_reads, sg_truth_bam, sg_depth_add, sg_variants_add, sg_errtab_add) are
+ * refused with SG_ERR_INVALID.                                                                    */
 int sg_sample(sg_ctx* ctx);
 /* Wait for the pass and report sizes: FASTQ bytes for mate 1 / mate 2 (0 for SE) and the number
  * of fragments actually produced (pairs for PE, reads for SE).                                   */
 int sg_result(sg_ctx* ctx, uint64_t* bytes_r1, uint64_t* bytes_r2, uint64_t* n_fragments);
 /* Copy the FASTQ text to host buffers (the bytes SeqWriter::write(char*,char*) would receive,
- * lib/seqwriter/SeqWriter.cpp:41-54).  host_r2 may be NULL for SE.                               */
+ * lib/seqwriter/SeqWriter.cpp:41-54).  host_r2 may be NULL for SE.  sg_fetch, sg_fetch_range and
+ * sg_device_output wait for the pass as sg_result does: straight after sg_sample they give the
+ * complete text.                                                                                 */
 int sg_fetch(sg_ctx* ctx, char* host_r1, char* host_r2);
 /* Partial copy for pipelined sinks: bytes [offset, offset+bytes) of mate 0/1's FASTQ text.  With a
  * destination from sg_host_alloc (pinned) the copy runs at PCIe speed.                            */

@@ -249,10 +249,19 @@ static int finish_plan(sg_ctx* ctx, uint64_t nw, uint32_t n_segs, uint32_t n_slo
   B.meta = ctx->meta.as<uint4>();
   B.totals = ctx->totals.as<uint64_t>();
   B.slowq_count = (uint32_t*)(B.totals + 4);
-  ctx->have_plan = true;
-  ctx->sampled = false;
-  ctx->results_valid = false;
+  ctx->pass = sg_ctx::Pass(sg_ctx::Pass::Planned);
   return SG_OK;
+}
+
+// The chains or the profile changed: the plan is gone, and a pass's rows no longer belong to them (its text stays).
+static void retire_plan(sg_ctx* ctx) {
+  if (ctx->pass.stage <= sg_ctx::Pass::Planned) ctx->pass = sg_ctx::Pass();
+  else ctx->pass.rows_current = false;
+}
+
+// The pass is over (its outputs were detached, or it failed): back to its plan, if that is still good.
+static void restart_pass(sg_ctx* ctx) {
+  ctx->pass = sg_ctx::Pass(ctx->pass.rows_current ? sg_ctx::Pass::Planned : sg_ctx::Pass::None);
 }
 
 // 2-bit copies of the chains buffer (`total` bytes, a multiple of 1024) for the straight-line emit kernel
@@ -300,7 +309,7 @@ static int commit_chains(sg_ctx* ctx, sg_ctx::ChainLayout&& L) {
   ctx->B.chain_len = ctx->chain_meta.as<uint64_t>() + L.len.size();
   ctx->hap = std::move(L);
   ctx->have_haps = true;
-  ctx->have_plan = false;
+  retire_plan(ctx);
   return SG_OK;
 }
 
@@ -312,17 +321,22 @@ static int truth_need_map(sg_ctx* ctx, const char* who) {
   return SG_OK;
 }
 
+static int rows_need_current(sg_ctx* ctx, const char* who) {
+  if (ctx->pass.rows_current) return SG_OK;
+  return ctx->fail(SG_ERR_INVALID, std::string(who) + ": the chains or the profile changed since sg_sample");
+}
+
 int sg_pass_prelude(sg_ctx* ctx, const char* who, sg::PieceMap* map, bool bam_names) {
+  if (int rc = rows_need_current(ctx, who)) return rc;
   if (map)
     if (int rc = truth_need_map(ctx, who)) return rc;
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call sg_result first");
+  if (int rc = sg_pass_need(ctx, who, sg_ctx::Pass::Settled)) return rc;
   const sg::DevBatch& B = ctx->B;
   const uint32_t nm = B.paired ? 2 : 1;
   if (map && (uint64_t)B.n_slots * nm >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 reads in one pass");
   if (bam_names && B.prefix_len > 200) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": read names longer than a BAM record holds");
   if (B.diag)
     return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": the pass ran under SG_DIAG (a timing ablation: its reads are not those of their rows)");
-  SG_HIP(hipSetDevice(ctx->device));
   if (map) {
     const size_t n_chains = ctx->hap.len.size();
     map->chain_first = ctx->truth.map.as<uint64_t>();
@@ -704,7 +718,7 @@ int sg_load_prepared_profile(sg_ctx* ctx, const sg_profile_tables* Tp) {
     for (int m = 1; m <= T.kmer; m++) { P.kmer_off[m] = off; p *= 4; off += p; }
   }
   ctx->have_profile = true;
-  ctx->have_plan = false;
+  retire_plan(ctx);
   return SG_OK;
 }
 
@@ -721,9 +735,8 @@ int sg_load_profile(sg_ctx* ctx, const sg_profile_cdf* pr) {
 // detached outputs
 // ------------------------------------------------------------------------------------------------
 int sg_detach_outputs(sg_ctx* ctx, sg_outputs** out) {
-  if (!ctx || !out) return SG_ERR_INVALID;
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_detach_outputs: call sg_result first");
-  SG_HIP(hipSetDevice(ctx->device));
+  if (!out) return SG_ERR_INVALID;
+  if (int rc = sg_pass_need(ctx, "sg_detach_outputs", sg_ctx::Pass::Settled)) return rc;
   sg_outputs* o = nullptr;
   if (!ctx->spare.empty()) { o = ctx->spare.back(); ctx->spare.pop_back(); }
   if (!o) {
@@ -735,14 +748,12 @@ int sg_detach_outputs(sg_ctx* ctx, sg_outputs** out) {
   // whatever the spare still holds goes back to the context (it is empty or smaller than what was just used)
   std::swap(ctx->out1, o->text[0]); std::swap(ctx->out2, o->text[1]);
   std::swap(ctx->gz1, o->gz[0]); std::swap(ctx->gz2, o->gz[1]);
-  o->text_bytes[0] = ctx->host_totals[0];
-  o->text_bytes[1] = ctx->B.paired ? ctx->host_totals[1] : 0;
-  o->gz_bytes[0] = ctx->gz_valid ? ctx->gz_bytes[0] : 0;
-  o->gz_bytes[1] = ctx->gz_valid ? ctx->gz_bytes[1] : 0;
-  ctx->results_valid = false;
-  ctx->sampled = false;
-  ctx->gz_valid = false;
-  ctx->truth.valid = false;
+  const sg_ctx::Pass& Q = ctx->pass;
+  o->text_bytes[0] = Q.host_totals[0];
+  o->text_bytes[1] = ctx->B.paired ? Q.host_totals[1] : 0;
+  o->gz_bytes[0] = Q.gz_bytes[0];   // (0 without sg_compress)
+  o->gz_bytes[1] = Q.gz_bytes[1];
+  restart_pass(ctx);
   *out = o;
   return SG_OK;
 }
@@ -902,21 +913,24 @@ static int deflate_text(sg_ctx* ctx, const uint8_t* text, uint64_t bytes, DevBuf
 }
 
 int sg_compress(sg_ctx* ctx, uint64_t* gz_bytes_r1, uint64_t* gz_bytes_r2) {
-  if (!ctx) return SG_ERR_INVALID;
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_compress: call sg_result first");
-  SG_HIP(hipSetDevice(ctx->device));
+  if (int rc = sg_pass_need(ctx, "sg_compress", sg_ctx::Pass::Settled)) return rc;
+  sg_ctx::Pass& Q = ctx->pass;
   const int nm = ctx->B.paired ? 2 : 1;
-  ctx->gz_bytes[0] = ctx->gz_bytes[1] = 0;
+  Q.have_gz = false;   // (a call that fails half-way leaves no members and no sizes)
+  Q.gz_bytes[0] = Q.gz_bytes[1] = 0;
+  uint64_t gz[2] = {0, 0};
   for (int m = 0; m < nm; m++) {
-    const uint64_t bytes = ctx->host_totals[m];
+    const uint64_t bytes = Q.host_totals[m];
     if (!bytes) continue;
     const uint8_t* text = m == 0 ? ctx->out1.as<uint8_t>() : ctx->out2.as<uint8_t>();
-    const int rc = deflate_text(ctx, text, bytes, m == 0 ? ctx->gz1 : ctx->gz2, &ctx->gz_bytes[m], "sg_compress");
+    const int rc = deflate_text(ctx, text, bytes, m == 0 ? ctx->gz1 : ctx->gz2, &gz[m], "sg_compress");
     if (rc != SG_OK) return rc;
   }
-  ctx->gz_valid = true;
-  if (gz_bytes_r1) *gz_bytes_r1 = ctx->gz_bytes[0];
-  if (gz_bytes_r2) *gz_bytes_r2 = ctx->gz_bytes[1];
+  Q.have_gz = true;
+  Q.gz_bytes[0] = gz[0];
+  Q.gz_bytes[1] = gz[1];
+  if (gz_bytes_r1) *gz_bytes_r1 = Q.gz_bytes[0];
+  if (gz_bytes_r2) *gz_bytes_r2 = Q.gz_bytes[1];
   return SG_OK;
 }
 
@@ -939,8 +953,8 @@ int sg_deflate_bgzf(sg_ctx* ctx, const void* text, uint64_t bytes, void* out, ui
 
 int sg_fetch_compressed(sg_ctx* ctx, int mate, uint64_t offset, uint64_t bytes, void* host_dst) {
   if (!ctx || mate < 0 || mate > 1 || (bytes && !host_dst)) return SG_ERR_INVALID;
-  if (!ctx->gz_valid || !ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_fetch_compressed: call sg_compress first");
-  if (offset + bytes > ctx->gz_bytes[mate]) return ctx->fail(SG_ERR_INVALID, "sg_fetch_compressed: range past the end of the compressed text");
+  if (!ctx->pass.have_gz) return ctx->fail(SG_ERR_INVALID, "sg_fetch_compressed: call sg_compress first");
+  if (offset + bytes > ctx->pass.gz_bytes[mate]) return ctx->fail(SG_ERR_INVALID, "sg_fetch_compressed: range past the end of the compressed text");
   SG_HIP(hipSetDevice(ctx->device));
   if (bytes) {
     const uint8_t* src = (mate == 0 ? ctx->gz1.as<uint8_t>() : ctx->gz2.as<uint8_t>()) + offset;
@@ -1034,7 +1048,7 @@ int sg_truth_map(sg_ctx* ctx, const sg_hap_piece* pieces, const uint8_t* seg_fir
     at = 0;
   }
   T.mapped = false;   // (a copy that fails half-way leaves no map rather than a mixed one)
-  T.valid = false;
+  ctx->pass.have_bam = false;   // (records of another map)
   const size_t first_b = sg::truth_map_pieces_at(n_chains);
   SG_ENSURE(T.map, first_b + dev.size() * sizeof(sg::TruthPiece) + 64);
   SG_HIP(hipMemcpyAsync(T.map.p, chain_first.data(), (n_chains + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1063,12 +1077,12 @@ static_assert(sizeof(sg_truth_read) == sizeof(sg::TruthReadRow), "sg_truth_read 
 
 int sg_truth_reads(sg_ctx* ctx, int mate, uint32_t first_slot, uint32_t n, sg_truth_read* out) {
   if (!ctx || mate < 0 || mate > 1 || (n && !out)) return SG_ERR_INVALID;
+  if (int rc = rows_need_current(ctx, "sg_truth_reads")) return rc;
   if (int rc = truth_need_map(ctx, "sg_truth_reads")) return rc;
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_truth_reads: call sg_result first");
+  if (int rc = sg_pass_need(ctx, "sg_truth_reads", sg_ctx::Pass::Settled)) return rc;
   if (mate == 1 && !ctx->B.paired) return ctx->fail(SG_ERR_INVALID, "sg_truth_reads: a single-end pass has no mate 2");
   if ((uint64_t)first_slot + n > ctx->B.n_slots) return ctx->fail(SG_ERR_INVALID, "sg_truth_reads: slots past the end of the batch");
   if (!n) return SG_OK;
-  SG_HIP(hipSetDevice(ctx->device));
   SG_ENSURE(ctx->truth.rows, (size_t)n * sizeof(sg::TruthReadRow));
   sg::launch_truth_reads(ctx->P, ctx->B, (uint32_t)mate, first_slot, n, ctx->truth.rows.as<sg::TruthReadRow>(), ctx->stream);
   return sg_read_back(ctx, out, ctx->truth.rows.p, (size_t)n * sizeof(sg::TruthReadRow));
@@ -1080,10 +1094,11 @@ int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
   memset(&J, 0, sizeof J);
   if (int rc = sg_pass_prelude(ctx, "sg_truth_bam", &J.map, true)) return rc;
   sg_ctx::Truth& T = ctx->truth;
+  sg_ctx::Pass& Q = ctx->pass;
   const sg::DevBatch& B = ctx->B;
   const uint32_t N = J.map.n_reads;
-  T.valid = false;
-  T.rec_bytes = T.gz_bytes = T.records = T.unmapped = 0;
+  Q.have_bam = false;
+  Q.bam_rec_bytes = Q.bam_gz_bytes = Q.bam_records = Q.bam_unmapped = 0;
   hipStream_t s = ctx->stream;
   // the pack kernel's stages: one record's FASTQ text and one record's image, for reads of up to L + 512 bases
   const uint32_t np_cap = (uint32_t)ctx->P.L + 512u;
@@ -1117,22 +1132,22 @@ int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
     uint64_t flags = 0;
     if (int rc = sg_read_back(ctx, &flags, wk + 16, 8)) return rc;
     if (flags & 4) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: a record does not fit the record kernel's stages");
-    if (int rc = deflate_text(ctx, T.rec.as<uint8_t>(), total, T.gz, &T.gz_bytes, "sg_truth_bam")) return rc;
+    if (int rc = deflate_text(ctx, T.rec.as<uint8_t>(), total, T.gz, &Q.bam_gz_bytes, "sg_truth_bam")) return rc;
   }
-  T.rec_bytes = total;
-  T.records = c[0];
-  T.unmapped = c[1];
-  T.valid = true;
-  if (record_bytes) *record_bytes = T.rec_bytes;
-  if (bgzf_bytes) *bgzf_bytes = T.gz_bytes;
+  Q.bam_rec_bytes = total;
+  Q.bam_records = c[0];
+  Q.bam_unmapped = c[1];
+  Q.have_bam = true;
+  if (record_bytes) *record_bytes = Q.bam_rec_bytes;
+  if (bgzf_bytes) *bgzf_bytes = Q.bam_gz_bytes;
   return SG_OK;
 }
 
 int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes, void* host_dst) {
   if (!ctx || (bytes && !host_dst)) return SG_ERR_INVALID;
   if (int rc = truth_need_map(ctx, "sg_fetch_truth")) return rc;
-  if (!ctx->truth.valid) return ctx->fail(SG_ERR_INVALID, "sg_fetch_truth: call sg_truth_bam first");
-  if (offset + bytes > (compressed ? ctx->truth.gz_bytes : ctx->truth.rec_bytes)) return ctx->fail(SG_ERR_INVALID, "sg_fetch_truth: range past the end of the data");
+  if (!ctx->pass.have_bam) return ctx->fail(SG_ERR_INVALID, "sg_fetch_truth: call sg_truth_bam first");
+  if (offset + bytes > (compressed ? ctx->pass.bam_gz_bytes : ctx->pass.bam_rec_bytes)) return ctx->fail(SG_ERR_INVALID, "sg_fetch_truth: range past the end of the data");
   SG_HIP(hipSetDevice(ctx->device));
   if (bytes) {
     const uint8_t* src = (compressed ? ctx->truth.gz : ctx->truth.rec).as<uint8_t>() + offset;
@@ -1145,9 +1160,9 @@ int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes,
 int sg_truth_info(sg_ctx* ctx, uint64_t* records, uint64_t* unmapped) {
   if (!ctx) return SG_ERR_INVALID;
   if (int rc = truth_need_map(ctx, "sg_truth_info")) return rc;
-  if (!ctx->truth.valid) return ctx->fail(SG_ERR_INVALID, "sg_truth_info: call sg_truth_bam first");
-  if (records) *records = ctx->truth.records;
-  if (unmapped) *unmapped = ctx->truth.unmapped;
+  if (!ctx->pass.have_bam) return ctx->fail(SG_ERR_INVALID, "sg_truth_info: call sg_truth_bam first");
+  if (records) *records = ctx->pass.bam_records;
+  if (unmapped) *unmapped = ctx->pass.bam_unmapped;
   return SG_OK;
 }
 
@@ -1378,7 +1393,7 @@ static int launch_text(sg_ctx* ctx, bool prof) {
   B.out_cap[1] = ctx->out2.cap;
   // Queue of the items the fast emit kernel leaves to the generic code (windows with a non-ACGT base,
   // reads with >= 2 sequencing indels): room for every item of ~10 % of the reads.  A batch that
-  // needs more is emitted again by the generic kernel (sg_result), so the size is not a correctness
+  // needs more is emitted again by the generic kernel (settle_pass), so the size is not a correctness
   // matter.  SG_SLOWQ_CAP overrides it (tests force the overflow path with it).
   B.slowq = nullptr;
   B.slowq_cap = 0;
@@ -1392,13 +1407,14 @@ static int launch_text(sg_ctx* ctx, bool prof) {
   }
   if (prof) SG_HIP(hipEventRecord(ctx->evs[5], s));  // after the (first-pass) output allocation
   sg::launch_header(ctx->P, B, s);
-  ctx->emit_path = sg::emit_path(ctx->P, B, false);
+  ctx->pass.emit_path = sg::emit_path(ctx->P, B, false);
   sg::launch_emit(ctx->P, B, s, false, prof ? ctx->evs[7] : nullptr);
   if (prof) SG_HIP(hipEventRecord(ctx->evs[6], s));
   return SG_OK;
 }
 
 static int run_pass(sg_ctx* ctx) {
+  sg_ctx::Pass& Q = ctx->pass = sg_ctx::Pass(sg_ctx::Pass::Planned);   // whatever the last pass left ends here
   sg::DevBatch& B = ctx->B;
   B.k0 = (uint32_t)ctx->seed;
   B.k1 = (uint32_t)(ctx->seed >> 32);
@@ -1426,43 +1442,40 @@ static int run_pass(sg_ctx* ctx) {
   }
   // The FASTQ size is only known now, on the device.  When the context already holds output buffers (every pass
   // but a context's first), the emit kernels are launched at once: they compare the size with the buffers' capacity
-  // themselves and do nothing but raise a flag when it does not fit (finish_pass then grows the buffers and launches
+  // themselves and do nothing but raise a flag when it does not fit (settle_pass then grows the buffers and launches
   // them again).  Otherwise two u64 are read back first -- one stream sync in the middle of the pass.
-  ctx->speculative = ctx->out1.p != nullptr && (!B.paired || ctx->out2.p != nullptr) && getenv("SG_NO_SPECULATION") == nullptr;
-  if (!ctx->speculative) {
+  Q.speculative = ctx->out1.p != nullptr && (!B.paired || ctx->out2.p != nullptr) && getenv("SG_NO_SPECULATION") == nullptr;
+  if (!Q.speculative) {
     sg::launch_mail(B.totals, ctx->mail, s);
     SG_HIP(hipStreamSynchronize(s));
-    memcpy(ctx->host_totals, ctx->mail, 4 * 8);
-    if (ctx->host_totals[3] & 1) return ctx->fail(SG_ERR_OVERFLOW, "sg_sample: a read drew more than SG_MAX_EVENTS sequencing indels");
-    SG_ENSURE(ctx->out1, ctx->host_totals[0] + 64);
-    if (B.paired) SG_ENSURE(ctx->out2, ctx->host_totals[1] + 64);
+    memcpy(Q.host_totals, ctx->mail, 4 * 8);
+    if (Q.host_totals[3] & 1) return ctx->fail(SG_ERR_OVERFLOW, "sg_sample: a read drew more than SG_MAX_EVENTS sequencing indels");
+    SG_ENSURE(ctx->out1, Q.host_totals[0] + 64);
+    if (B.paired) SG_ENSURE(ctx->out2, Q.host_totals[1] + 64);
   }
   if (int rc = launch_text(ctx, prof)) return rc;
   sg::launch_mail(B.totals, ctx->mail, s);
   SG_HIP(hipGetLastError());
-  ctx->sampled = true;
-  ctx->pass_pending = true;
-  ctx->results_valid = false;
-  ctx->gz_valid = false;
+  Q.stage = sg_ctx::Pass::Queued;
   return SG_OK;
 }
 
-// What a queued pass left: sizes, flags; the emit kernels again if the text did not fit the buffers they were given.
-static int finish_pass(sg_ctx* ctx) {
-  if (!ctx->pass_pending) return SG_OK;
+// Queued -> Settled.  What the queued pass left: sizes, flags; the emit kernels again if the text did not fit the buffers
+// they were given; every item again through the generic kernel if the slow queue overflowed; the kernel times.
+static int settle_pass(sg_ctx* ctx) {
+  sg_ctx::Pass& Q = ctx->pass;
+  sg::DevBatch& B = ctx->B;
   SG_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->pass_pending = false;
-  memcpy(ctx->host_totals, ctx->mail, 4 * 8);
-  ctx->host_flags[0] = ctx->mail[3];
-  ctx->host_flags[1] = ctx->mail[4];
-  if (ctx->host_totals[3] & 1) {
-    ctx->sampled = false;
+  memcpy(Q.host_totals, ctx->mail, 4 * 8);
+  Q.host_flags[0] = ctx->mail[3];
+  Q.host_flags[1] = ctx->mail[4];
+  if (Q.host_totals[3] & 1) {
+    restart_pass(ctx);
     return ctx->fail(SG_ERR_OVERFLOW, "sg_sample: a read drew more than SG_MAX_EVENTS sequencing indels");
   }
-  if (ctx->speculative && (ctx->host_flags[0] & 4)) {  // the buffers were too small: grow, emit again
-    sg::DevBatch& B = ctx->B;
-    SG_ENSURE(ctx->out1, ctx->host_totals[0] + 64);
-    if (B.paired) SG_ENSURE(ctx->out2, ctx->host_totals[1] + 64);
+  if (Q.speculative && (Q.host_flags[0] & 4)) {  // the buffers were too small: grow, emit again
+    SG_ENSURE(ctx->out1, Q.host_totals[0] + 64);
+    if (B.paired) SG_ENSURE(ctx->out2, Q.host_totals[1] + 64);
     // what the aborted launch left behind: the flags, the slow-queue counts (a mate whose text did fit has appended its
     // items already) and the read-group counters of both emit kernels (exhausted by that mate); the record offsets' segment
     // bases and the sizes stay
@@ -1471,10 +1484,35 @@ static int finish_pass(sg_ctx* ctx) {
     if (int rc = launch_text(ctx, ctx->profiling)) return rc;   // (the kernel times are then those of the launch that counted)
     sg::launch_mail(B.totals, ctx->mail, ctx->stream);
     SG_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->host_flags[0] = ctx->mail[3];
-    ctx->host_flags[1] = ctx->mail[4];
+    Q.host_flags[0] = ctx->mail[3];
+    Q.host_flags[1] = ctx->mail[4];
   }
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  Q.slow_items = (Q.host_flags[1] & 0xFFFFFFFFu) + (Q.host_flags[1] >> 32);
+  Q.slow_overflow = (Q.host_flags[0] & 2) != 0;
+  if (Q.slow_overflow) {  // headers are in place; every item again through the generic kernel
+    sg::launch_emit(ctx->P, B, ctx->stream, true, nullptr);
+    SG_HIP(hipGetLastError());
+    SG_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  if (ctx->profiling) {
+    for (int i = 0; i < 4; i++) SG_HIP(hipEventElapsedTime(&ctx->last_ms[i], ctx->evs[i], ctx->evs[i + 1]));
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT], ctx->evs[5], ctx->evs[7]));
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT_SLOW], ctx->evs[7], ctx->evs[6]));
+  }
+  Q.stage = sg_ctx::Pass::Settled;
   return SG_OK;
+}
+
+extern "C++" int sg_pass_need(sg_ctx* ctx, const char* who, sg_ctx::Pass::Stage at_least, bool settle_now) {   // (declared in sg_api.h, not part of the ABI)
+  using Pass = sg_ctx::Pass;
+  if (!ctx) return SG_ERR_INVALID;
+  static const char* const step[] = {"", "sg_plan", "sg_sample", "sg_result"};
+  const Pass::Stage need = settle_now && at_least == Pass::Settled ? Pass::Queued : at_least;   // settling asks no more
+  if (ctx->pass.stage < need || (at_least == Pass::Planned && !ctx->pass.rows_current))
+    return ctx->fail(SG_ERR_INVALID, std::string(who) + ": call " + step[need] + " first");
+  SG_HIP(hipSetDevice(ctx->device));
+  return at_least == Pass::Settled && ctx->pass.stage == Pass::Queued ? settle_pass(ctx) : SG_OK;
 }
 
 int sg_emit_variant(sg_ctx* ctx) {
@@ -1483,79 +1521,54 @@ int sg_emit_variant(sg_ctx* ctx) {
 }
 
 int sg_emit_path(const sg_ctx* ctx, sg_emit_path_info* info) {
-  if (!ctx || !info || !ctx->results_valid) return SG_ERR_INVALID;
-  info->main_kernel = ctx->emit_path.main_kernel;
-  info->slow_rows_lds = ctx->emit_path.slow_rows_lds;
-  info->lds_bytes = ctx->emit_path.lds_bytes;
-  info->clean_cap = ctx->emit_path.clean_cap;
+  // (a const context: no message to leave, no device to select, so the stage is tested here and not by sg_pass_need)
+  if (!ctx || !info || ctx->pass.stage != sg_ctx::Pass::Settled) return SG_ERR_INVALID;
+  const sg::EmitPath& path = ctx->pass.emit_path;
+  info->main_kernel = path.main_kernel;
+  info->slow_rows_lds = path.slow_rows_lds;
+  info->lds_bytes = path.lds_bytes;
+  info->clean_cap = path.clean_cap;
   return SG_OK;
 }
 
 int sg_emit_info(sg_ctx* ctx, uint64_t* queued_items, int* requeued) {
-  if (!ctx) return SG_ERR_INVALID;
-  if (!ctx->results_valid) return ctx->fail(SG_ERR_INVALID, "sg_emit_info: call sg_result first");
-  if (queued_items) *queued_items = ctx->slow_items;
-  if (requeued) *requeued = ctx->slow_overflow ? 1 : 0;
+  if (int rc = sg_pass_need(ctx, "sg_emit_info", sg_ctx::Pass::Settled)) return rc;
+  if (queued_items) *queued_items = ctx->pass.slow_items;
+  if (requeued) *requeued = ctx->pass.slow_overflow ? 1 : 0;
   return SG_OK;
 }
 
 int sg_sample(sg_ctx* ctx) {
-  if (!ctx) return SG_ERR_INVALID;
-  if (!ctx->have_plan) return ctx->fail(SG_ERR_INVALID, "sg_sample: call sg_plan first");
-  SG_HIP(hipSetDevice(ctx->device));
-  ctx->truth.valid = false;
+  if (int rc = sg_pass_need(ctx, "sg_sample", sg_ctx::Pass::Planned)) return rc;
   return run_pass(ctx);
 }
 
 int sg_result(sg_ctx* ctx, uint64_t* bytes_r1, uint64_t* bytes_r2, uint64_t* n_fragments) {
-  if (!ctx) return SG_ERR_INVALID;
-  if (!ctx->sampled) return ctx->fail(SG_ERR_INVALID, "sg_result: call sg_sample first");
-  SG_HIP(hipSetDevice(ctx->device));
-  if (int rc = finish_pass(ctx)) return rc;
-  SG_HIP(hipStreamSynchronize(ctx->stream));
-  if (!ctx->results_valid) {
-    ctx->slow_items = (ctx->host_flags[1] & 0xFFFFFFFFu) + (ctx->host_flags[1] >> 32);
-    ctx->slow_overflow = (ctx->host_flags[0] & 2) != 0;
-    if (ctx->slow_overflow) {  // headers are in place; every item again through the generic kernel
-      sg::launch_emit(ctx->P, ctx->B, ctx->stream, true, nullptr);
-      SG_HIP(hipGetLastError());
-      SG_HIP(hipStreamSynchronize(ctx->stream));
-    }
-  }
-  if (ctx->profiling) {
-    for (int i = 0; i < 4; i++) SG_HIP(hipEventElapsedTime(&ctx->last_ms[i], ctx->evs[i], ctx->evs[i + 1]));
-    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT], ctx->evs[5], ctx->evs[7]));
-    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT_SLOW], ctx->evs[7], ctx->evs[6]));
-  }
-  ctx->results_valid = true;
-  if (bytes_r1) *bytes_r1 = ctx->host_totals[0];
-  if (bytes_r2) *bytes_r2 = ctx->B.paired ? ctx->host_totals[1] : 0;
-  if (n_fragments) *n_fragments = ctx->host_totals[2];
+  if (int rc = sg_pass_need(ctx, "sg_result", sg_ctx::Pass::Settled, true)) return rc;
+  const uint64_t* totals = ctx->pass.host_totals;
+  if (bytes_r1) *bytes_r1 = totals[0];
+  if (bytes_r2) *bytes_r2 = ctx->B.paired ? totals[1] : 0;
+  if (n_fragments) *n_fragments = totals[2];
   return SG_OK;
 }
 
 int sg_fetch(sg_ctx* ctx, char* host_r1, char* host_r2) {
-  if (!ctx) return SG_ERR_INVALID;
-  if (!ctx->sampled) return ctx->fail(SG_ERR_INVALID, "sg_fetch: call sg_sample first");
-  SG_HIP(hipSetDevice(ctx->device));
-  if (int rc = finish_pass(ctx)) return rc;
-  if (host_r1 && ctx->host_totals[0])
-    SG_HIP(hipMemcpyAsync(host_r1, ctx->out1.p, ctx->host_totals[0], hipMemcpyDeviceToHost, ctx->stream));
-  if (host_r2 && ctx->B.paired && ctx->host_totals[1])
-    SG_HIP(hipMemcpyAsync(host_r2, ctx->out2.p, ctx->host_totals[1], hipMemcpyDeviceToHost, ctx->stream));
+  if (int rc = sg_pass_need(ctx, "sg_fetch", sg_ctx::Pass::Settled, true)) return rc;
+  const uint64_t* totals = ctx->pass.host_totals;
+  if (host_r1 && totals[0])
+    SG_HIP(hipMemcpyAsync(host_r1, ctx->out1.p, totals[0], hipMemcpyDeviceToHost, ctx->stream));
+  if (host_r2 && ctx->B.paired && totals[1])
+    SG_HIP(hipMemcpyAsync(host_r2, ctx->out2.p, totals[1], hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   return SG_OK;
 }
 
 int sg_fetch_range(sg_ctx* ctx, int mate, uint64_t offset, uint64_t bytes, char* host_dst) {
   if (!ctx || (bytes && !host_dst) || mate < 0 || mate > 1) return SG_ERR_INVALID;
-  if (!ctx->sampled) return ctx->fail(SG_ERR_INVALID, "sg_fetch_range: call sg_sample first");
+  if (int rc = sg_pass_need(ctx, "sg_fetch_range", sg_ctx::Pass::Settled, true)) return rc;
   if (mate == 1 && !ctx->B.paired) return ctx->fail(SG_ERR_INVALID, "sg_fetch_range: single-end batch has no mate 2");
-  SG_HIP(hipSetDevice(ctx->device));
-  if (int rc = finish_pass(ctx)) return rc;
-  if (offset + bytes > ctx->host_totals[mate]) return ctx->fail(SG_ERR_INVALID, "sg_fetch_range: range past the end of the FASTQ text");
+  if (offset + bytes > ctx->pass.host_totals[mate]) return ctx->fail(SG_ERR_INVALID, "sg_fetch_range: range past the end of the FASTQ text");
   if (!bytes) return SG_OK;
-  SG_HIP(hipSetDevice(ctx->device));
   const char* src = (const char*)(mate ? ctx->out2.p : ctx->out1.p) + offset;
   SG_HIP(hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
@@ -1589,10 +1602,8 @@ int sg_host_free(sg_ctx* ctx, void* host_ptr) {
 }
 
 int sg_device_output(sg_ctx* ctx, void** dev_r1, void** dev_r2) {
-  if (!ctx) return SG_ERR_INVALID;
-  if (!ctx->sampled) return ctx->fail(SG_ERR_INVALID, "sg_device_output: call sg_sample first");
-  SG_HIP(hipSetDevice(ctx->device));
-  if (int rc = finish_pass(ctx)) return rc;   // a pass queued without its size may still move to larger buffers
+  // (settled here: a pass queued without its size may still move to larger buffers)
+  if (int rc = sg_pass_need(ctx, "sg_device_output", sg_ctx::Pass::Settled, true)) return rc;
   if (dev_r1) *dev_r1 = ctx->out1.p;
   if (dev_r2) *dev_r2 = ctx->B.paired ? ctx->out2.p : nullptr;
   return SG_OK;
@@ -1753,7 +1764,9 @@ int sg_plan_windows(sg_ctx* ctx, uint32_t store_id, const sg_window_gen* gens, u
   }
   for (uint32_t a = 0; a < n_active; a++) slots_out[a] = pi.slot_first[a + 1] - pi.slot_first[a];
   pi.valid = true;
-  ctx->have_plan = false;
+  // a batch planned from the table this one replaces is not sampled any more; a pass already sampled keeps its rows
+  // (ctx->windows is untouched until sg_plan_range)
+  if (ctx->pass.stage == sg_ctx::Pass::Planned) ctx->pass = sg_ctx::Pass();
   return SG_OK;
 }
 

@@ -46,7 +46,7 @@ struct sg_ctx {
   uint64_t seed = 0;
   std::string err;
 
-  bool have_profile = false, have_haps = false, have_plan = false, sampled = false;
+  bool have_profile = false, have_haps = false;   // the inputs; everything about a batch and its pass is in `pass`
   sg::DevProfile P{};
   sg::DevBatch B{};
   DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_actual, win_namebase, events, recoff, meta, totals, bsum,
@@ -59,8 +59,6 @@ struct sg_ctx {
     std::vector<uint64_t> off, len;
     size_t total = 0;   // bytes of the padded chains buffer
   } hap;
-  uint64_t gz_bytes[2] = {0, 0};
-  bool gz_valid = false;
   // Each truth output's state owns its device buffers: ending one is assigning a fresh state over it.
   // truth alignments (sg_truth_*): whether the chains came from a copy list (sg_build_haplotypes; how many pieces it
   // had) and, once sg_truth_map has been given that list, its pieces sorted by (chain, dst) with the chains' first
@@ -69,10 +67,9 @@ struct sg_ctx {
   // buffers (forget).
   struct TruthInfo {
     uint64_t n_given = 0;
-    bool from_build = false, mapped = false, valid = false;
+    bool from_build = false, mapped = false;
     std::vector<sg_truth_piece> sorted;
     std::vector<uint64_t> chain_first;
-    uint64_t rec_bytes = 0, gz_bytes = 0, records = 0, unmapped = 0;
   };
   struct Truth : TruthInfo {
     DevBuf map, work, rec, gz, rows;
@@ -123,15 +120,38 @@ struct sg_ctx {
   uint64_t ref_raw_bytes = 0;
   sg_train_session* train = nullptr;   // profile training in progress (sg_train_begin .. sg_train_finish / sg_train_end)
   std::vector<sg::DevContig> ref_contigs;  // host copy of the committed contig table
-  uint64_t host_totals[4] = {0, 0, 0, 0};
-  uint64_t host_flags[2] = {0, 0};  // totals[3..4] after the emit kernels: flags, slow-queue counts
-  uint64_t* mail = nullptr;         // pinned: where a pass's totals[0..4] land (copied to the two arrays above by finish_pass)
-  bool pass_pending = false;        // a pass is queued whose totals have not been looked at yet
-  bool speculative = false;         // ... and its emit kernels were launched before the text size was known (see run_pass)
-  uint64_t slow_items = 0;
-  bool slow_overflow = false;
-  sg::EmitPath emit_path = {0, -1, 0, 0};  // the emit kernels of the last pass (sg_emit_path)
-  bool results_valid = false;
+  uint64_t* mail = nullptr;   // pinned: where a pass's totals[0..4] land (copied into `pass` when it is settled)
+  // A batch and its sampling pass: the stage, and every fact whose meaning ends with the pass.  The buffers those facts
+  // describe stay where they are (out1 / out2, gz1 / gz2, truth.rec / truth.gz).  Starting over is assigning a fresh Pass.
+  //
+  //   None --sg_plan*--> Planned --sg_sample--> Queued --sg_pass_need(.., Settled, true)--> Settled
+  //
+  //   Planned  a batch is planned (finish_plan)
+  //   Queued   run_pass has enqueued the kernels; sizes are not looked at yet, the text may not have fitted its buffers
+  //   Settled  the stream is drained, totals / flags are the mail's, a text that did not fit and an overflowed slow queue
+  //            have been emitted again, slow_items / slow_overflow and (when profiling) the kernel times are taken
+  //
+  //   sg_plan*, sg_sample           a fresh Pass; so does a pass that fails with SG_ERR_OVERFLOW, and sg_detach_outputs
+  //                                 (both back to Planned: the plan is still good)
+  //   new chains, a new profile     Planned goes back to None; a Queued or Settled pass stays for the calls that read only
+  //                                 its text, with rows_current = false: its plan is gone (sg_sample: "call sg_plan
+  //                                 first") and its rows no longer belong to the chains, the piece map or the profile
+  //                                 (sg_pass_prelude and sg_truth_reads refuse)
+  struct Pass {
+    enum Stage { None, Planned, Queued, Settled } stage;
+    explicit Pass(Stage s = None) : stage(s) {}
+    bool rows_current = true;
+    bool speculative = false;         // the emit kernels were launched before the text size was known (see run_pass)
+    uint64_t host_totals[4] = {0, 0, 0, 0};
+    uint64_t host_flags[2] = {0, 0};  // totals[3..4] after the emit kernels: flags, slow-queue counts
+    uint64_t slow_items = 0;
+    bool slow_overflow = false;
+    sg::EmitPath emit_path = {0, -1, 0, 0};  // the emit kernels of the pass (sg_emit_path)
+    bool have_gz = false;             // sg_compress: gz1 / gz2 hold gz_bytes of members
+    uint64_t gz_bytes[2] = {0, 0};
+    bool have_bam = false;            // sg_truth_bam: truth.rec / truth.gz hold the pass's records
+    uint64_t bam_rec_bytes = 0, bam_gz_bytes = 0, bam_records = 0, bam_unmapped = 0;
+  } pass;
 
   bool profiling = false;
   hipEvent_t evs[8] = {};  // 0-3 starts of plan..scan, 4 end of scan, 5 start of emit, 6 end of emit, 7 between the two emit kernels
@@ -159,11 +179,16 @@ struct sg_ctx {
 
 // ---- what the truth outputs' entry points share (sg_truth_bam, sg_depth_*, sg_variants_*, sg_errtab_*) ----
 namespace sg { struct PieceMap; }
-// The start of a call that reads the pass just sampled, with today's checks in today's order: with `map`, the chains'
-// piece map (sg_build_haplotypes, then sg_truth_map); sg_result; with `map`, fewer than 2^32 reads; with `bam_names`, read
-// names that a BAM record holds (sg_truth_bam's own check, whose place is in front of the next); no SG_DIAG.  Then the
-// device is selected and *map filled.  Defined in sg_api.cpp.
+// The start of a call that reads the rows of the pass just sampled, its checks in this order: rows that still belong to
+// the chains and the profile; with `map`, the chains' piece map (sg_build_haplotypes, then sg_truth_map); sg_result; with
+// `map`, fewer than 2^32 reads; with `bam_names`, read names that a BAM record holds (sg_truth_bam's own check, whose
+// place is in front of the next); no SG_DIAG.  The device is selected and *map filled.  Defined in sg_api.cpp.
 int sg_pass_prelude(sg_ctx* ctx, const char* who, sg::PieceMap* map, bool bam_names = false);
+// The gate of every call that reads a pass: no context; "<who>: call sg_plan / sg_sample / sg_result first" when the
+// stage is below `at_least`; then the device is selected.  Settled is asked in two ways: of a pass that sg_result has
+// settled already (a Queued one is told to call sg_result), or with settle_now, which settles a Queued pass here and
+// so asks no more than sg_sample of the caller.  Planned asks for a plan that new inputs have not retired.
+int sg_pass_need(sg_ctx* ctx, const char* who, sg_ctx::Pass::Stage at_least, bool settle_now = false);
 // no context, or a call in front of its output's X_begin
 inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
   if (!ctx) return SG_ERR_INVALID;
