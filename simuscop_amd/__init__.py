@@ -89,6 +89,20 @@ class SgGcWindow(C.Structure):
     _fields_ = [("start", C.c_uint64), ("chain", C.c_uint32), ("len", C.c_uint32)]
 
 
+class SgGcModel(C.Structure):
+    """sg_gc_model: the GC-bias model of sg_window_weights / sg_windows_build"""
+    _fields_ = [("means", C.POINTER(C.c_double)), ("std", C.c_double), ("quantiles", C.POINTER(C.c_double)), ("lg_cells", C.c_uint32),
+                ("frag_size", C.c_uint32), ("full_tile_form", C.c_int32), ("ctx24", C.c_uint32)]
+
+
+class SgWindowGen(C.Structure):
+    _fields_ = [("hap_base", C.c_uint64), ("hap_len", C.c_uint64), ("chain", C.c_uint32), ("seg", C.c_uint32), ("first_window", C.c_uint64)]
+
+
+class SgActiveSeg(C.Structure):
+    _fields_ = [("reads", C.c_int64), ("weight", C.c_double), ("seg_size", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class SgContig(C.Structure):
     _fields_ = [("raw_offset", C.c_uint64), ("length", C.c_uint64), ("line_bases", C.c_uint32), ("line_width", C.c_uint32)]
 
@@ -235,6 +249,15 @@ def load_engine():
     lib.sg_host_free.argtypes = [vp, vp]
     lib.sg_device_output.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     lib.sg_gc_percent.argtypes = [vp, C.POINTER(SgGcWindow), C.c_uint64, C.POINTER(C.c_int32)]
+    lib.sg_window_weights.argtypes = [vp, C.POINTER(SgGcWindow), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(SgGcModel),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    lib.sg_windows_build.argtypes = [vp, C.c_uint32, C.POINTER(SgWindowGen), C.c_uint64, C.c_uint32, C.POINTER(SgGcModel), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_uint64)]
+    lib.sg_plan_windows.argtypes = [vp, C.c_uint32, C.POINTER(SgWindowGen), C.c_uint64, C.POINTER(SgActiveSeg), C.c_uint32, C.c_uint32, C.c_uint32,
+                                    C.c_int32, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.sg_plan_range.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.sg_windows_drop.argtypes = [vp]
+    lib.sg_windows_drop.restype = None
     lib.sg_set_profiling.argtypes = [vp, C.c_int]
     lib.sg_kernel_times.argtypes = [vp, C.POINTER(C.c_float)]
     lib.sg_emit_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
