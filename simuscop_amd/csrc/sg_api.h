@@ -1,7 +1,7 @@
 // sg_api.h -- what the files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
-// sink, reference, haplotypes, window planner), sg_api_train.cpp (profile training, BGZF / BAM input) and
-// sg_api_depth.cpp (true coverage), sg_api_variants.cpp (true allele counts) and sg_api_errors.cpp (true error counts).  Internal: the
-// ABI itself is include/simuscop_amd.h.
+// sink, reference, haplotypes), sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM
+// input), sg_api_depth.cpp (true coverage), sg_api_variants.cpp (true allele counts) and sg_api_errors.cpp (true error
+// counts).  Internal: the ABI itself is include/simuscop_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,7 +50,7 @@ struct sg_ctx {
   sg::DevProfile P{};
   sg::DevBatch B{};
   DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_actual, win_namebase, events, recoff, meta, totals, bsum,
-      out1, out2, gcw, gco, gcm, slowq, ref_raw, ref_codes, ref_meta, hap_work, gz1, gz2, gz_work,
+      out1, out2, slowq, ref_raw, ref_codes, ref_meta, hap_work, gz1, gz2, gz_work,
       infl_src, infl_meta, infl_out, infl_crc,   // sg_inflate_bgzf (infl_crc also serves the training session's BAM input)
       defl_src, defl_out;                        // sg_deflate_bgzf: the caller's text and its members
   // the haplotype chains in `chains` (sg_upload_haplotypes, sg_build_haplotypes): chain c holds len[c] bases from off[c] on;
@@ -104,19 +104,27 @@ struct sg_ctx {
     DevBuf table;
   } errtab;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
-  // device-made sampling plan: window weights per store id (sg_windows_build), the batch table of sg_plan_windows
-  std::map<uint32_t, DevBuf> wstore;
-  std::map<uint32_t, uint64_t> wstore_n;
-  DevBuf wplan, wwork;
-  struct PlanInfo {
-    bool valid = false;
-    uint64_t n_windows = 0;
-    uint32_t n_active = 0, batch_id = 0;
-    int32_t paired = 0;
-    std::string prefix;
-    std::vector<uint32_t> seg_first, seg_size;  // per active segment (seg_first has n_active + 1 entries)
-    std::vector<uint64_t> slot_first;           // planned fragments before each active segment; [n_active] = total
-  } winfo;
+  // the window planner (sg_gc_percent, sg_window_weights, sg_windows_*, sg_plan_windows / sg_plan_range;
+  // sg_api_windows.cpp): `stores` holds the window weights of sg_windows_build per store id, `plan` the batch table of
+  // sg_plan_windows (sg_window rows) and `info` what sg_plan_range needs of it on the host.  `gc` (sg_gc_percent,
+  // sg_window_weights) and `work` (sg_windows_build, sg_plan_windows) are arenas private to one call, `model` the means
+  // and quantile knots of a call's sg_gc_model.  The stores and the batch table survive new chains: store ids are per
+  // (population, chromosome), and the driver uploads chromosomes in turn between sg_windows_build and sg_plan_windows.
+  // Only sg_windows_drop ends the stores.
+  struct Windows {
+    struct Store { DevBuf weights; uint64_t n = 0; };
+    struct PlanInfo {
+      bool valid = false;
+      uint32_t n_active = 0, batch_id = 0;
+      int32_t paired = 0;
+      std::string prefix;
+      std::vector<uint32_t> seg_first, seg_size;  // per active segment (seg_first has n_active + 1 entries)
+      std::vector<uint64_t> slot_first;           // planned fragments before each active segment; [n_active] = total
+    };
+    std::map<uint32_t, Store> stores;
+    DevBuf plan, work, gc, model;
+    PlanInfo info;
+  } win;
   uint64_t ref_raw_bytes = 0;
   sg_train_session* train = nullptr;   // profile training in progress (sg_train_begin .. sg_train_finish / sg_train_end)
   std::vector<sg::DevContig> ref_contigs;  // host copy of the committed contig table
@@ -189,6 +197,10 @@ int sg_pass_prelude(sg_ctx* ctx, const char* who, sg::PieceMap* map, bool bam_na
 // settled already (a Queued one is told to call sg_result), or with settle_now, which settles a Queued pass here and
 // so asks no more than sg_sample of the caller.  Planned asks for a plan that new inputs have not retired.
 int sg_pass_need(sg_ctx* ctx, const char* who, sg_ctx::Pass::Stage at_least, bool settle_now = false);
+// Work buffers and DevBatch fields of a batch whose windows / segment arrays are in ctx->windows / ctx->segmeta: the end
+// of sg_plan and sg_plan_range.  Internal like the two above, not part of the ABI.  Defined in sg_api.cpp.
+int finish_plan(sg_ctx* ctx, uint64_t nw, uint32_t n_segs, uint32_t n_slots, uint32_t batch_id, uint32_t first_window,
+                uint32_t first_slot, int32_t paired, const char* name_prefix);
 // no context, or a call in front of its output's X_begin
 inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
   if (!ctx) return SG_ERR_INVALID;
@@ -209,4 +221,20 @@ int sg_run_counted(sg_ctx* ctx, void* counters, size_t n, uint64_t* out, Launch 
   SG_HIP(hipMemsetAsync(counters, 0, n * 8, ctx->stream));
   launch();
   return sg_read_back(ctx, out, counters, n * 8);
+}
+// One device allocation carved into arrays, each 64-byte aligned.  `carve` takes its arrays from the arena it is given;
+// it runs twice: without a base for the size, then over `buf` grown to that size for the pointers.
+struct SgArena {
+  uintptr_t base;
+  size_t off = 0;
+  template <class T> T* take(size_t count) { T* p = (T*)(base + off); off = (off + count * sizeof(T) + 63) & ~(size_t)63; return p; }
+};
+template <class Carve>
+int sg_carve(sg_ctx* ctx, DevBuf& buf, Carve carve) {
+  SgArena size{0};
+  carve(size);
+  if (int e = buf.ensure(size.off)) return ctx->hipfail((hipError_t)e, "hipMalloc(arena)");
+  SgArena a{(uintptr_t)buf.p};
+  carve(a);
+  return SG_OK;
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sg_api.h"
+#include "sg_scan.h"
 #include "sg_truth.h"
 
 static_assert(sizeof(sg_depth_run) == sizeof(sg::DepthRun), "sg_depth_run is the kernel's row");

@@ -13,6 +13,7 @@
 
 #include "sg_api.h"
 #include "sg_bam.h"
+#include "sg_scan.h"
 #include "sg_train.h"
 
 extern "C" {

@@ -107,7 +107,7 @@ struct DevBatch {
   uint64_t out_cap[2];
 };
 
-// ---- launchers (sg_kernels.hip) ----
+// ---- launchers of the sampling pass (sg_kernels.hip); the window planner's are in sg_windows.h, the scan's in sg_scan.h ----
 void launch_plan(const DevProfile& P, const DevBatch& B, hipStream_t s);
 void launch_namebase(const DevBatch& B, hipStream_t s);
 void launch_indel(const DevProfile& P, const DevBatch& B, hipStream_t s);
@@ -122,21 +122,6 @@ int emit_variant(const DevProfile& P);
 struct EmitPath { int main_kernel; int slow_rows_lds; uint32_t lds_bytes, clean_cap; };
 EmitPath emit_path(const DevProfile& P, const DevBatch& B, bool force_generic);
 uint32_t record_seg_shift(uint32_t n_slots);
-uint32_t scan_blocks(uint32_t n);
-void launch_scan_u32(const uint32_t* in, uint32_t n, uint64_t* bsum, uint64_t* out, uint64_t* total, hipStream_t s);
 void launch_encode(uint8_t* buf, size_t bytes, hipStream_t s);
-void launch_gc(const uint8_t* chains, const uint64_t* chain_off, const sg_gc_window* wins, uint64_t n, int32_t* out, hipStream_t s);
-void launch_tile(const sg_window_gen* gens, const uint64_t* prefix, uint32_t n_gens, uint64_t n, uint32_t frag, const uint64_t* seg_first,
-                 sg_gc_window* out, uint32_t* seg_ord, uint32_t* win_ord, hipStream_t s);
-void launch_seg_sum(const double* wt, const uint64_t* seg_first, uint32_t n_segs, double* out, hipStream_t s);
-void launch_window_reads(const sg_window_gen* gens, const uint64_t* prefix, uint32_t n_gens, uint64_t n, uint32_t frag, const double* wt,
-                         const sg_active_seg* act, const uint32_t* seg_first, uint32_t n_act, sg_window* rows, unsigned long long* seg_sum,
-                         int32_t paired, uint32_t* planned, hipStream_t s);
-void launch_slot_base(sg_window* rows, uint64_t n, const uint64_t* off, const uint32_t* seg_first, uint32_t n_act, const uint64_t* total,
-                      uint64_t* seg_slots, hipStream_t s);
-void launch_slice(const sg_window* all, uint64_t w_lo, uint64_t n, uint32_t a0, uint32_t slot_lo, sg_window* out, hipStream_t s);
-void launch_gc_weight(const int32_t* gc, const sg_gc_window* wins, const uint32_t* seg_ord, const uint32_t* win_ord, uint64_t n,
-                      const double* means, double std, const double* Q, uint32_t lg_cells, uint32_t frag, int32_t full_tile_form,
-                      uint32_t ctx24, uint64_t seed, double* out, hipStream_t s);
 
 }  // namespace sg

@@ -15,47 +15,15 @@
 //   emit_fast_kernel, emit_slow_kernel, emit_kernel (generic) + header_kernel
 //                    Profile::predict sampling loop  (Profile.cpp:1636-1700) + FASTQ formatting
 //                    (Segment.cpp:803-832)
-//   gc_kernel        calculateGCPercent              (lib/mydefine/MyDefine.cpp:279-303)
+// The window planner's kernels are in sg_windows.hip, the general u32 scan in sg_scan.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 #include "sg_device.h"
+#include "sg_philox.h"
 
 namespace sg {
-
-// ------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11), one call = four 32-bit draws
-// ------------------------------------------------------------------------------------------------
-template <int ROUNDS>
-__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                           uint32_t k0, uint32_t k1, uint32_t out[4]) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-#pragma unroll
-  for (int r = 0; r < ROUNDS; r++) {
-    const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;  // one v_mad_u64_u32 each
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c0 = __builtin_amdgcn_bitop3_b32(hi1, c1, k0, 0x96);  // three-input xor in one v_bitop3_b32
-    c1 = lo1;
-    c2 = __builtin_amdgcn_bitop3_b32(hi0, c3, k1, 0x96);
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-  philox4x32<10>(c0, c1, c2, c3, k0, k1, out);
-}
-// the per-base draws (KIND_BASE): kBaseRounds rounds (sg_device.h)
-__device__ __forceinline__ void philox_base(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-  philox4x32<kBaseRounds>(c0, c1, c2, c3, k0, k1, out);
-}
-
-__device__ __forceinline__ uint32_t dev_ctx(uint32_t kind, uint32_t mate, uint32_t batch) {
-  return kind | ((((mate & 1u) << 23) | (batch & 0xFFFFu)) << 8);
-}
 
 // lower bound over a {k0, T...} row (sg_tables.h)
 __device__ __forceinline__ uint32_t row_search(const uint32_t* __restrict__ row, uint32_t lg, uint32_t x) {
@@ -475,77 +443,6 @@ __global__ __launch_bounds__(256) void header_kernel(DevBatch B) {
   if (!(B.diag & 4u)) write_name(B.out[m] + ooff, B.prefix, B.prefix_len, m0.z, m0.w, B.paired, m);
 }
 
-// ------------------------------------------------------------------------------------------------
-// exclusive scan u32 -> u64 (three passes, 2048 items per block), one grid row per mate
-// ------------------------------------------------------------------------------------------------
-#define SCAN_ITEMS 8
-#define SCAN_BLOCK 256
-#define SCAN_TILE (SCAN_ITEMS * SCAN_BLOCK)
-
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total) {
-  __shared__ uint64_t wsum[SCAN_BLOCK / 64];
-  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint64_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint64_t t = __shfl_up(incl, d);
-    if ((int)lane >= d) incl += t;
-  }
-  if (lane == 63) wsum[wid] = incl;
-  __syncthreads();
-  uint64_t woff = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < SCAN_BLOCK / 64; i++) {
-    if (i < (int)wid) woff += wsum[i];
-    tot += wsum[i];
-  }
-  __syncthreads();
-  *total = tot;
-  return woff + incl - v;
-}
-
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_reduce_kernel(const uint32_t* __restrict__ in, uint32_t n,
-                                                                uint64_t* __restrict__ bsum, uint32_t nblk) {
-  const uint32_t m = blockIdx.y;
-  const uint32_t* src = in + (size_t)m * n;
-  const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  uint64_t s = 0;
-#pragma unroll
-  for (int i = 0; i < SCAN_ITEMS; i++)
-    if (base + i < n) s += src[base + i];
-  uint64_t tot;
-  block_exclusive_scan(s, &tot);
-  if (threadIdx.x == 0) bsum[(size_t)m * nblk + blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(1024) void scan_sums_kernel(uint64_t* __restrict__ bsum, uint32_t nblk,
-                                                        uint64_t* __restrict__ totals) {
-  // one block per row (mate): thread i owns a run of ceil(nblk / 1024) consecutive sums -- adds them up, the 1024 run
-  // totals are scanned in LDS (one Hillis-Steele pass), then every thread writes the exclusive prefixes of its run
-  __shared__ uint64_t buf[1024];
-  const uint32_t m = blockIdx.x;
-  uint64_t* b = bsum + (size_t)m * nblk;
-  const uint32_t run = (nblk + 1023u) / 1024u;
-  const uint32_t lo = threadIdx.x * run, hi = min(lo + run, nblk);
-  uint64_t mine = 0;
-  for (uint32_t i = lo; i < hi; i++) mine += b[i];
-  buf[threadIdx.x] = mine;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {
-    const uint64_t t = threadIdx.x >= d ? buf[threadIdx.x - d] : 0;
-    __syncthreads();
-    buf[threadIdx.x] += t;
-    __syncthreads();
-  }
-  uint64_t carry = buf[threadIdx.x] - mine;
-  for (uint32_t i = lo; i < hi; i++) {
-    const uint64_t v = b[i];
-    b[i] = carry;
-    carry += v;
-  }
-  if (threadIdx.x == 1023u) totals[m] = buf[1023];
-}
-
 // Record offsets, middle level: the block sums indel_kernel left in blkbase, cut into <= 16 segments of 2^seg_shift
 // blocks; workgroup j scans segment j in place (thread i owns a run of consecutive sums), the workgroup that arrives
 // last turns the 16 segment totals into segment bases and the mate's text size (totals[m]).  One launch, 16 CUs per
@@ -592,29 +489,6 @@ __global__ __launch_bounds__(1024) void block_base_kernel(DevBatch B) {
       acc += v;
     }
     B.totals[m] = acc;
-  }
-}
-
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const uint32_t* __restrict__ in, uint32_t n,
-                                                               const uint64_t* __restrict__ bsum, uint32_t nblk,
-                                                               uint64_t* __restrict__ out) {
-  const uint32_t m = blockIdx.y;
-  const uint32_t* src = in + (size_t)m * n;
-  uint64_t* dst = out + (size_t)m * n;
-  const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-  uint32_t v[SCAN_ITEMS];
-  uint64_t s = 0;
-#pragma unroll
-  for (int i = 0; i < SCAN_ITEMS; i++) {
-    v[i] = base + i < n ? src[base + i] : 0u;
-    s += v[i];
-  }
-  uint64_t tot;
-  uint64_t off = block_exclusive_scan(s, &tot) + bsum[(size_t)m * nblk + blockIdx.x];
-#pragma unroll
-  for (int i = 0; i < SCAN_ITEMS; i++) {
-    if (base + i < n) dst[base + i] = off;
-    off += v[i];
   }
 }
 
@@ -2126,205 +2000,6 @@ __global__ __launch_bounds__(256) void encode_kernel(uint4* __restrict__ buf, si
 }
 
 // ------------------------------------------------------------------------------------------------
-// GC% per window: one wave per window, 16 B per lane per step
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t count_eq_bytes(uint32_t w, uint32_t c) {
-  uint32_t x = w ^ (c * 0x01010101u);
-  uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
-  t = ~(t | x | 0x7F7F7F7Fu);  // 0x80 in every byte of x that is zero
-  return __popc(t);
-}
-
-__global__ __launch_bounds__(256) void gc_kernel(const uint8_t* __restrict__ chains, const uint64_t* __restrict__ chain_off,
-                                                 const sg_gc_window* __restrict__ wins, uint64_t n, int32_t* __restrict__ out) {
-  const uint64_t w = (uint64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63;
-  if (w >= n) return;
-  const sg_gc_window win = wins[w];
-  const uint8_t* p = chains + chain_off[win.chain] + win.start;
-  uint32_t gc = 0, nn = 0;
-  for (uint32_t b = lane * 16; b < win.len; b += 64 * 16) {
-    uint32_t v[4];
-    __builtin_memcpy(v, p + b, 16);
-    const uint32_t rem = win.len - b;  // bytes of this 16-byte group inside the window
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      uint32_t x = v[i];
-      const int left = (int)rem - 4 * i;
-      if (left <= 0) x = 0;
-      else if (left < 4) x &= (1u << (8 * left)) - 1u;  // masked-off bytes read as 0 = 'A': neither GC nor N
-      gc += count_eq_bytes(x, 1u) + count_eq_bytes(x, 3u);  // encoded C, G
-      nn += count_eq_bytes(x, 4u);                           // encoded N
-    }
-  }
-#pragma unroll
-  for (int d = 32; d; d >>= 1) {
-    gc += __shfl_xor(gc, d);
-    nn += __shfl_xor(nn, d);
-  }
-  if (lane == 0) out[w] = win.len == 0 ? 0 : (nn > 0 ? -1 : (int32_t)(100u * gc / win.len));
-}
-
-// GC factor and weight of a window (Profile::getGCFactor, Profile.cpp:1507-1517; Segment.cpp:576,586,615): one lane
-// per window, the normal variate interpolated from the quantile table in three rounded fp64 operations (no fused
-// multiply-add: the host / oracle evaluation of the same table must give the same bits)
-__global__ __launch_bounds__(256) void gc_weight_kernel(const int32_t* __restrict__ gc, const sg_gc_window* __restrict__ wins,
-                                                        const uint32_t* __restrict__ seg_ord, const uint32_t* __restrict__ win_ord,
-                                                        uint64_t n, const double* __restrict__ means, double std,
-                                                        const double* __restrict__ Q, uint32_t lg_cells, uint32_t frag,
-                                                        int32_t full_tile_form, uint32_t c3, uint32_t k0, uint32_t k1,
-                                                        double* __restrict__ out) {
-  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= n) return;
-  const int32_t g = gc[w];
-  double f = 0.0;
-  if (g >= 0 && g <= 100) {
-    const double mean = means[g];
-    const uint32_t tail_bits = 32u - lg_cells;
-    const double scale = 1.0 / (double)(1ull << (tail_bits + 1u));
-    for (uint32_t a = 0;; a++) {
-      uint32_t x[4];
-      philox4x32_10(win_ord[w], a, seg_ord[w], c3, k0, k1, x);
-      const uint32_t k = x[0] >> tail_bits, fr = x[0] & ((1u << tail_bits) - 1u);
-      const double t = __dmul_rn((double)(2u * fr + 1u), scale);
-      const double d = __dsub_rn(Q[k + 1], Q[k]);
-      const double z = __dadd_rn(Q[k], __dmul_rn(d, t));
-      f = __dadd_rn(mean, __dmul_rn(std, z));
-      if (f >= 0.0) break;
-    }
-  }
-  const uint32_t len = wins[w].len;
-  out[w] = (full_tile_form && len == frag) ? __ddiv_rn(f, (double)frag)
-                                           : __ddiv_rn(__dmul_rn(f, (double)len), (double)((uint64_t)frag * frag));
-}
-
-// ------------------------------------------------------------------------------------------------
-// sampling plan on the device (sg_windows_build / sg_plan_windows / sg_plan_range)
-// ------------------------------------------------------------------------------------------------
-// generator of window w: the last one whose prefix (first window) is <= w
-__device__ __forceinline__ uint32_t gen_of(const uint64_t* __restrict__ prefix, uint32_t n_gens, uint64_t w) {
-  uint32_t lo = 0, hi = n_gens - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (prefix[mid] <= w) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// lane = window: geometry of the tile (Segment.cpp:566-590), its segment and its ordinal inside the segment
-__global__ __launch_bounds__(256) void tile_kernel(const sg_window_gen* __restrict__ gens, const uint64_t* __restrict__ prefix,
-                                                   uint32_t n_gens, uint64_t n, uint32_t frag, const uint64_t* __restrict__ seg_first,
-                                                   sg_gc_window* __restrict__ out, uint32_t* __restrict__ seg_ord, uint32_t* __restrict__ win_ord) {
-  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= n) return;
-  const uint32_t g = gen_of(prefix, n_gens, w);
-  const sg_window_gen G = gens[g];
-  const uint64_t t = w - prefix[g], off = t * frag;
-  sg_gc_window o;
-  o.start = G.hap_base + off;
-  o.chain = G.chain;
-  o.len = (uint32_t)(G.hap_len - off < frag ? G.hap_len - off : frag);
-  out[w] = o;
-  seg_ord[w] = G.seg;
-  win_ord[w] = (uint32_t)(w - seg_first[G.seg]);
-}
-// workgroup = segment: weight sum in window order (the reference's summation order, Segment.cpp:627-630; fp64 addition
-// does not reassociate).  The whole workgroup stages tiles of the weights in LDS (coalesced), its first lane adds them
-// one after the other: the chain of dependent adds is all that is serial (one lane per segment reading its weights
-// from memory itself took 0.27 ms for 65 segments of 2000 windows).
-#define SEG_SUM_TILE 4096
-__global__ __launch_bounds__(256) void seg_sum_kernel(const double* __restrict__ wt, const uint64_t* __restrict__ seg_first, uint32_t n_segs,
-                                                      double* __restrict__ out) {
-  __shared__ double tile[SEG_SUM_TILE];
-  const uint32_t k = blockIdx.x;
-  const uint64_t w0 = seg_first[k], w1 = seg_first[k + 1];
-  double acc = 0.0;
-  for (uint64_t base = w0; base < w1; base += SEG_SUM_TILE) {
-    const uint32_t n = (uint32_t)(w1 - base < SEG_SUM_TILE ? w1 - base : SEG_SUM_TILE);
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) tile[i] = wt[base + i];
-    __syncthreads();
-    if (threadIdx.x == 0u)
-      for (uint32_t i = 0; i < n; i++) acc = __dadd_rn(acc, tile[i]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0u) out[k] = acc;
-}
-// lane = window of an active segment: fragRCs[i] = (long)(fragWeights[i] * readCount / totalWL), Segment.cpp:466-470
-__global__ __launch_bounds__(256) void window_reads_kernel(const sg_window_gen* __restrict__ gens, const uint64_t* __restrict__ prefix,
-                                                           uint32_t n_gens, uint64_t n, uint32_t frag, const double* __restrict__ wt,
-                                                           const sg_active_seg* __restrict__ act, sg_window* __restrict__ rows,
-                                                           unsigned long long* __restrict__ seg_sum) {
-  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool valid = w < n;
-  uint32_t seg = 0xFFFFFFFFu;
-  long long rc = 0;
-  if (valid) {
-    const uint32_t g = gen_of(prefix, n_gens, w);
-    const sg_window_gen G = gens[g];
-    const uint64_t t = w - prefix[g], off = t * frag;
-    const sg_active_seg A = act[G.seg];
-    const double total = __dadd_rn(A.weight, 2.2204e-16);
-    rc = (long long)__ddiv_rn(__dmul_rn(wt[G.first_window + t], (double)A.reads), total);
-    sg_window o;
-    o.hap_base = G.hap_base;
-    o.chain = G.chain;
-    o.spos = (uint32_t)off;
-    o.len = (uint32_t)(G.hap_len - off < frag ? G.hap_len - off : frag);
-    o.n_reads = (int32_t)rc;
-    o.seg = G.seg;
-    o.slot_base = 0;
-    rows[w] = o;
-    seg = G.seg;
-  }
-  // The segment's sum (an integer: any order): a wave's windows are nearly always of ONE segment -- one atomic for the
-  // wave then, not 64 on the same address (64 k single-address atomics were 0.37 ms of this kernel's 0.38).
-  const uint32_t seg0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg);  // (the first lane of a wave that has one is valid)
-  if (__ballot(valid && seg != seg0) == 0ull) {
-    unsigned long long sum = (unsigned long long)rc;  // 0 on the lanes past n
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_down(sum, d, 64);
-    if ((threadIdx.x & 63u) == 0u && valid) atomicAdd(seg_sum + seg0, sum);
-  } else if (valid) {
-    atomicAdd(seg_sum + seg, (unsigned long long)rc);
-  }
-}
-// lane = active segment: the remainder goes to the segment's first window (Segment.cpp:472-474)
-__global__ __launch_bounds__(64) void seg_remainder_kernel(const sg_active_seg* __restrict__ act, const uint32_t* __restrict__ seg_first,
-                                                           uint32_t n_act, const unsigned long long* __restrict__ seg_sum,
-                                                           sg_window* __restrict__ rows) {
-  const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= n_act) return;
-  const long long sum = (long long)seg_sum[a];
-  if (sum < act[a].reads) rows[seg_first[a]].n_reads += (int32_t)(act[a].reads - sum);
-}
-__global__ __launch_bounds__(256) void planned_kernel(const sg_window* __restrict__ rows, uint64_t n, int32_t paired, uint32_t* __restrict__ planned) {
-  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= n) return;
-  const int32_t r = rows[w].n_reads;
-  planned[w] = r <= 0 ? 0u : (paired ? ((uint32_t)r + 1u) / 2u : (uint32_t)r);
-}
-__global__ __launch_bounds__(256) void slot_base_kernel(sg_window* __restrict__ rows, uint64_t n, const uint64_t* __restrict__ off) {
-  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w < n) rows[w].slot_base = (uint32_t)off[w];
-}
-// planned fragments before each active segment's first window (and the total in [n_act])
-__global__ __launch_bounds__(64) void seg_slots_kernel(const uint64_t* __restrict__ off, const uint32_t* __restrict__ seg_first, uint32_t n_act,
-                                                       const uint64_t* __restrict__ total, uint64_t* __restrict__ out) {
-  const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a < n_act) out[a] = off[seg_first[a]];
-  if (a == n_act) out[a] = *total;
-}
-// rows [w_lo, w_lo + n) of the batch table as a batch of their own: segment ordinals and slots relative to the run
-__global__ __launch_bounds__(256) void slice_kernel(const sg_window* __restrict__ all, uint64_t w_lo, uint64_t n, uint32_t a0, uint32_t slot_lo,
-                                                    sg_window* __restrict__ out) {
-  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= n) return;
-  sg_window o = all[w_lo + w];
-  o.seg -= a0;
-  o.slot_base -= slot_lo;
-  out[w] = o;
-}
-
-// ------------------------------------------------------------------------------------------------
 // launchers (declared in sg_device.h)
 // ------------------------------------------------------------------------------------------------
 // a pass's sizes and flags (totals[0..4]) to the context's pinned mailbox: a kernel of five lanes writing host memory
@@ -2355,7 +2030,6 @@ void launch_header(const DevProfile& P, const DevBatch& B, hipStream_t s) {
   dim3 grid((B.n_slots + 255) / 256, B.paired ? 2 : 1);
   hipLaunchKernelGGL(header_kernel, grid, dim3(256), 0, s, B);
 }
-uint32_t scan_blocks(uint32_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 uint32_t record_seg_shift(uint32_t n_slots) {  // smallest shift with at most 16 segments of 2^shift blocks of 256 reads
   const uint32_t nblk = (n_slots + 255u) >> 8;
   uint32_t k = 0;
@@ -2365,14 +2039,6 @@ uint32_t record_seg_shift(uint32_t n_slots) {  // smallest shift with at most 16
 void launch_scan(const DevBatch& B, hipStream_t s) {  // block sums of indel_kernel -> block / segment bases, text sizes
   if (!B.n_slots) return;
   hipLaunchKernelGGL(block_base_kernel, dim3(16, B.paired ? 2 : 1), dim3(1024), 0, s, B);
-}
-// exclusive scan of n u32 values into u64 offsets (one row); total -> *total
-void launch_scan_u32(const uint32_t* in, uint32_t n, uint64_t* bsum, uint64_t* out, uint64_t* total, hipStream_t s) {
-  if (!n) return;
-  const uint32_t nblk = scan_blocks(n);
-  hipLaunchKernelGGL(scan_reduce_kernel, dim3(nblk, 1), dim3(SCAN_BLOCK), 0, s, in, n, bsum, nblk);
-  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, s, bsum, nblk, total);
-  hipLaunchKernelGGL(scan_apply_kernel, dim3(nblk, 1), dim3(SCAN_BLOCK), 0, s, in, n, bsum, nblk, out);
 }
 // LDS budget: the generic kernels stage the substitution rows when they fit (the alias columns are read through L2);
 // the straight-line kernel needs its whole table image.
@@ -2498,43 +2164,6 @@ void launch_encode(uint8_t* buf, size_t bytes, hipStream_t s) {  // bytes is a m
   const size_t n16 = bytes / 16;
   uint32_t grid = (uint32_t)std::min<size_t>((n16 + 255) / 256, 256 * 16);
   hipLaunchKernelGGL(encode_kernel, dim3(grid), dim3(256), 0, s, (uint4*)buf, n16);
-}
-void launch_gc_weight(const int32_t* gc, const sg_gc_window* wins, const uint32_t* seg_ord, const uint32_t* win_ord, uint64_t n,
-                      const double* means, double std, const double* Q, uint32_t lg_cells, uint32_t frag, int32_t full_tile_form,
-                      uint32_t ctx24, uint64_t seed, double* out, hipStream_t s) {
-  if (!n) return;
-  hipLaunchKernelGGL(gc_weight_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, gc, wins, seg_ord, win_ord, n, means, std, Q,
-                     lg_cells, frag, full_tile_form, KIND_GC | (ctx24 << 8), (uint32_t)seed, (uint32_t)(seed >> 32), out);
-}
-static inline uint32_t blocks256(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-void launch_tile(const sg_window_gen* gens, const uint64_t* prefix, uint32_t n_gens, uint64_t n, uint32_t frag, const uint64_t* seg_first,
-                 sg_gc_window* out, uint32_t* seg_ord, uint32_t* win_ord, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(tile_kernel, dim3(blocks256(n)), dim3(256), 0, s, gens, prefix, n_gens, n, frag, seg_first, out, seg_ord, win_ord);
-}
-void launch_seg_sum(const double* wt, const uint64_t* seg_first, uint32_t n_segs, double* out, hipStream_t s) {
-  if (n_segs) hipLaunchKernelGGL(seg_sum_kernel, dim3(n_segs), dim3(256), 0, s, wt, seg_first, n_segs, out);
-}
-void launch_window_reads(const sg_window_gen* gens, const uint64_t* prefix, uint32_t n_gens, uint64_t n, uint32_t frag, const double* wt,
-                         const sg_active_seg* act, const uint32_t* seg_first, uint32_t n_act, sg_window* rows, unsigned long long* seg_sum,
-                         int32_t paired, uint32_t* planned, hipStream_t s) {
-  if (!n) return;
-  hipLaunchKernelGGL(window_reads_kernel, dim3(blocks256(n)), dim3(256), 0, s, gens, prefix, n_gens, n, frag, wt, act, rows, seg_sum);
-  hipLaunchKernelGGL(seg_remainder_kernel, dim3((n_act + 63) / 64), dim3(64), 0, s, act, seg_first, n_act, seg_sum, rows);
-  hipLaunchKernelGGL(planned_kernel, dim3(blocks256(n)), dim3(256), 0, s, rows, n, paired, planned);
-}
-void launch_slot_base(sg_window* rows, uint64_t n, const uint64_t* off, const uint32_t* seg_first, uint32_t n_act, const uint64_t* total,
-                      uint64_t* seg_slots, hipStream_t s) {
-  if (!n) return;
-  hipLaunchKernelGGL(slot_base_kernel, dim3(blocks256(n)), dim3(256), 0, s, rows, n, off);
-  hipLaunchKernelGGL(seg_slots_kernel, dim3((n_act + 64) / 64), dim3(64), 0, s, off, seg_first, n_act, total, seg_slots);
-}
-void launch_slice(const sg_window* all, uint64_t w_lo, uint64_t n, uint32_t a0, uint32_t slot_lo, sg_window* out, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(slice_kernel, dim3(blocks256(n)), dim3(256), 0, s, all, w_lo, n, a0, slot_lo, out);
-}
-void launch_gc(const uint8_t* chains, const uint64_t* chain_off, const sg_gc_window* wins, uint64_t n, int32_t* out, hipStream_t s) {
-  if (!n) return;
-  uint32_t grid = (uint32_t)((n + 3) / 4);
-  hipLaunchKernelGGL(gc_kernel, dim3(grid), dim3(256), 0, s, chains, chain_off, wins, n, out);
 }
 
 }  // namespace sg

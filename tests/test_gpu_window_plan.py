@@ -100,6 +100,14 @@ class Ctx:
         assert rc == 0, self.err()
         return out.view(np.uint64), gc.tolist()
 
+    def gc_percent(self, rows):
+        """rows: (chain, start, len).  Returns the GC% of every window."""
+        w = np.zeros(len(rows), dtype=GC_WINDOW)
+        w["chain"], w["start"], w["len"] = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
+        gc = np.full(len(rows), -99, dtype=np.int32)
+        assert self.eng.sg_gc_percent(self.ctx, ptr(w, SgGcWindow), len(rows), ptr(gc, C.c_int32)) == 0, self.err()
+        return gc.tolist()
+
     @staticmethod
     def c_gens(gens):
         g = np.zeros(max(len(gens), 1), dtype=WINDOW_GEN)
@@ -257,6 +265,37 @@ def test_window_weights_refusals(eng):
         assert "sg_upload_haplotypes first" in c.window_weights([(0, 0, 16)], [0], [0], WM.model(16, lg_cells=12), want=1)
 
 
+def test_work_buffers_shared_by_calls_of_different_sizes(eng):
+    """sg_window_weights and sg_gc_percent carve one arena of the context, sg_windows_build another, and both keep the
+    size of the largest call: 8,193 windows, then 3, a build, 5, and 8,193 again on one context give, bit for bit, what
+    each call gives on a context of its own.  Two chains of 331 and 257 bases (an N in the first), windows of 16 and 37
+    bases at every start."""
+    c0 = bytearray(WM._letters(331, 7).tobytes())
+    c0[100] = ord("N")
+    small = [bytes(c0), WM._letters(257, 8).tobytes()]
+
+    def rows(n):
+        return [(i % 2, (i * 7) % (len(small[i % 2]) - 37), (16, 37)[(i // 2) % 2]) for i in range(n)]
+
+    m16, m37 = WM.model(16, lg_cells=14), WM.model(37)            # (tables of 2^14 and 2^12 cells)
+    gens = [WM.Gen(0, 300, 0, 0), WM.Gen(5, 200, 1, 1), WM.Gen(9, 37, 0, 3)]
+    calls = [lambda c: c.window_weights(rows(8193), *WM.explicit_ordinals(8193), m16),
+             lambda c: c.gc_percent(rows(3)),
+             lambda c: c.build(1, gens, 5, m16),
+             lambda c: c.window_weights(rows(5), *WM.explicit_ordinals(5), m37),
+             lambda c: c.gc_percent(rows(8193))]
+
+    def plain(r):
+        return [x.tolist() if isinstance(x, np.ndarray) else x for x in r] if isinstance(r, tuple) else r
+
+    with Ctx(eng, chains=small) as c:
+        shared = [plain(call(c)) for call in calls]
+    for i, call in enumerate(calls):
+        with Ctx(eng, chains=small) as c:
+            assert plain(call(c)) == shared[i], f"call {i}"
+    assert -1 in shared[4] and len(set(shared[4])) > 10 and shared[2][1] == 19 + 13 + 3 and any(shared[0][0])
+
+
 # ---- (b) sg_windows_build ---------------------------------------------------------------------------------------------------
 _BUILT = {}
 
@@ -341,7 +380,8 @@ def test_plan_windows_equals_the_model(eng, paired):
 
 def test_two_stores_alive_at_once(eng):
     """Store 1 (the frag-16 build) and store 2 (2,000 generators), then store 2 built again from other generators: plans
-    from either store equal the model before and after."""
+    from store 1, then store 2, then store 1 again equal the model before and after (the stores' sizes differ, and each
+    plan is checked against its own).  sg_windows_drop ends both."""
     gens, n_segs, note, t, w, seg_w = built(16)
     m2 = WM.model(16, lg_cells=12, ctx24=WM.CTX24S[1])
     with Ctx(eng, profile=True) as c:
@@ -354,9 +394,19 @@ def test_two_stores_alive_at_once(eng):
             ag2 = WM.active_gens(g2, t2, segs2)
             act2 = WM.active_rows(t2, sw2, segs2, "thousands")
             p2 = WM.plan(w2, ag2, act2, 16, 1)
-            assert c.plan_windows(2, ag2, act2, 16, 1) == (p2.slots, len(p2.rows))
+            ag1, act1, p1 = plan_case(WM.subset_segments(t), "thousands", 1)
+            for store, a_g, act, p in ((1, ag1, act1, p1), (2, ag2, act2, p2), (1, ag1, act1, p1)):
+                assert c.plan_windows(store, a_g, act, 16, 1) == (p.slots, len(p.rows)), store
+                c.plan_range(0, len(act))
+                dev = c.sample()                                  # the rows, through the text they cause
+                c.plan_host(p.rows, p.seg_first, len(act), 1)
+                assert dev[2] > 0 and same(dev, c.sample()), store
             ag, active, p = plan_case(WM.subset_segments(t), "thousands", 0)
             assert c.plan_windows(1, ag, active, 16, 0) == (p.slots, len(p.rows))
+            assert t.n != t2.n
+        eng.sg_windows_drop(c.ctx)
+        assert "no window weights under this store id" in c.plan_windows(1, ag, active, 16, 0, want=1)
+        assert "no window weights under this store id" in c.plan_windows(2, ag2, act2, 16, 1, want=1)
 
 
 def test_plan_refusals(eng):
