@@ -351,7 +351,7 @@ uint32_t sg_deflate_plan(const uint64_t lit_counts[286], const uint64_t dist_cou
  *                    SG_ERR_INVALID, as from every call below without a map
  *   sg_truth_pieces  the sorted pieces of one chain, as sg_truth_align takes them (contig: the one of sg_hap_piece)
  *   sg_truth_reads   after sg_result: where reads [first_slot, first_slot + n) of mate 0 / 1 came from
- *   sg_truth_bam     after sg_result, before sg_detach_outputs: the BAM records (SAMv1 section 4.2, no optional fields) of
+ *   sg_truth_bam     after sg_result, before sg_detach_outputs: the BAM records (SAMv1 section 4.2, no optional fields: see sg_truth_bam_tags) of
  *                    the pass's reads in FASTQ order -- slot by slot, mate 1 then mate 2; unused slots give nothing --
  *                    and their BGZF members (the compressor of sg_compress; no header, no EOF block).  QNAME is the FASTQ
  *                    name without '@' and "/1", SEQ / QUAL the FASTQ's, turned round for a reverse read; FLAG 0 / 16 (SE),
@@ -359,7 +359,41 @@ uint32_t sg_deflate_plan(const uint64_t lit_counts[286], const uint64_t dist_cou
  *                    for the leftmost mate).  An unmapped read: flag 0x4 without 0x10, MAPQ 0, no CIGAR, at its mate's
  *                    place (-1 / -1 without one); its mate gets 0x8 and loses 0x2, TLEN 0 for both.
  *   sg_fetch_truth   bytes [offset, offset + bytes) of the record stream (compressed = 0) or of its BGZF members (1)
- *   sg_truth_info    records and unmapped records of the last sg_truth_bam                                          */
+ *   sg_truth_info    records and unmapped records of the last sg_truth_bam
+ *
+ * Tags (simuReads --truth-tags; the rule: DESIGN.md "Truth tags").  Opt-in: sg_truth_bam makes the records above and
+ * launches the kernels it always has.
+ *   sg_truth_bam_tags  sg_truth_bam with optional fields behind the qualities, `tags` a mask of SG_TAG_NM | SG_TAG_MD |
+ *                    SG_TAG_XE (any subset; 0 is sg_truth_bam), in this order: NM:I on a mapped record (mismatching M
+ *                    bases + I + D bases), XE:I on a record whose template lies in its chain, mapped or not (the read's
+ *                    sequencing errors against the haplotype it was cut from: what it adds to Q.errors, I.bases and D.bases
+ *                    of the true error counts), MD:Z on a mapped record unless its text is longer than max_md bytes (only a
+ *                    long variant deletion inside the read makes one: the record keeps NM and XE and is counted in
+ *                    md_dropped).  block_size includes the tags.  The reference letter of MD is A C G T for those codes
+ *                    and N for anything else (the codes keep no IUPAC letter: the one difference from `samtools calmd`); a
+ *                    SEQ letter matches iff it equals it and is one of A C G T.  Same limits as sg_truth_bam, and templates
+ *                    of at most (max_md - 257) / 2 bases (SG_ERR_UNSUPPORTED); NM or MD without the codes of
+ *                    sg_reference_commit: SG_ERR_INVALID.  A read whose events or operations do not end at its length, or
+ *                    an alignment past its contig's end, fails the call (SG_ERR_INVALID)
+ *   sg_truth_tag_info  of the last sg_truth_bam / sg_truth_bam_tags: records with each tag, the sums of NM and XE, MD texts
+ *                    dropped, tag bytes, and max_md
+ *   sg_truth_tags    the rule for one record (host only, no context).  NM / MD: cigar (len << 4 | op), SEQ in BAM
+ *                    orientation, ref_codes = the contig's base codes (A0 C1 T2 G3, N 4, other 5, X 6) from POS on; the
+ *                    first min(md_len, md_cap) bytes of the text go to md (no NUL), a text longer than md_cap is dropped
+ *                    (*present lacks SG_TAG_MD).  n_ops == 0: an unmapped record, neither.  XE: tmpl_codes = the template's
+ *                    chain codes in chain direction (NULL: the template does not lie in its chain, no XE), reverse, the
+ *                    events (ev_pack form, read direction) and the read in FASTQ orientation.  *present = the tags the
+ *                    record gets                                                                                     */
+#define SG_TAG_NM 1u
+#define SG_TAG_MD 2u
+#define SG_TAG_XE 4u
+typedef struct sg_truth_tag_counts {
+  uint64_t n_nm, n_md, n_xe;   /* records with the tag                                           */
+  uint64_t nm_sum, xe_sum;
+  uint64_t md_dropped;         /* mapped records whose MD text was longer than max_md            */
+  uint64_t tag_bytes;
+  uint64_t max_md;
+} sg_truth_tag_counts;
 typedef struct sg_truth_piece {
   uint64_t dst;        /* offset in the chain                                                    */
   uint64_t src;        /* kind 0: 0-based position on contig `contig`                            */
@@ -388,6 +422,11 @@ int sg_truth_reads(sg_ctx* ctx, int mate, uint32_t first_slot, uint32_t n, sg_tr
 int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes);
 int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes, void* host_dst);
 int sg_truth_info(sg_ctx* ctx, uint64_t* records, uint64_t* unmapped);
+int sg_truth_bam_tags(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64_t* bgzf_bytes);
+int sg_truth_tag_info(sg_ctx* ctx, sg_truth_tag_counts* out);
+int sg_truth_tags(const uint32_t* cigar, uint32_t n_ops, const char* seq, uint32_t seq_len, const uint8_t* ref_codes, uint64_t n_ref,
+                  uint32_t md_cap, const uint8_t* tmpl_codes, uint32_t tmpl_len, int reverse, const uint32_t* events, uint32_t n_events,
+                  const char* read, uint32_t read_len, uint32_t* present, uint32_t* nm, char* md, uint32_t* md_len, uint32_t* xe);
 
 /* ---- true coverage: the depth the reads of all passes really laid down (simuReads --truth-depth) -------------------
  * Coverage adds up, so it needs no sort: one int32 difference array over the reference (len + 1 slots per contig, 4

@@ -32,6 +32,7 @@ ENGINE_SYMBOLS = [
     "sg_bgzf_members", "sg_inflate_bgzf", "sg_train_bam_start", "sg_train_feed_bgzf", "sg_train_bam_info",
     "sg_release_cached_memory",
     "sg_truth_align", "sg_truth_map", "sg_truth_pieces", "sg_truth_reads", "sg_truth_bam", "sg_fetch_truth", "sg_truth_info",
+    "sg_truth_bam_tags", "sg_truth_tag_info", "sg_truth_tags",
     "sg_depth_begin", "sg_depth_add", "sg_depth_add_spans", "sg_depth_bins", "sg_depth_runs", "sg_depth_fetch", "sg_depth_reset",
     "sg_depth_info", "sg_depth_end",
     "sg_variants_begin", "sg_variants_add", "sg_variants_counts", "sg_variants_reset", "sg_variants_info", "sg_variants_end",
@@ -124,6 +125,16 @@ class SgTruthRead(C.Structure):
                 ("tmpl_off", C.c_uint64), ("n_events", C.c_uint32), ("inside", C.c_uint32), ("events", C.c_uint32 * 32)]
 
 
+class SgTruthTagCounts(C.Structure):
+    """sg_truth_tag_counts: what the tags of the last truth_bam() came to (sg_truth_tag_info)"""
+    _fields_ = [("n_nm", C.c_uint64), ("n_md", C.c_uint64), ("n_xe", C.c_uint64), ("nm_sum", C.c_uint64), ("xe_sum", C.c_uint64),
+                ("md_dropped", C.c_uint64), ("tag_bytes", C.c_uint64), ("max_md", C.c_uint64)]
+
+
+TAG_NM, TAG_MD, TAG_XE = 1, 2, 4   # SG_TAG_*
+TAG_ALL = TAG_NM | TAG_MD | TAG_XE
+
+
 class SgDepthRun(C.Structure):
     """sg_depth_run: a run of equal depth starts at `start` (sg_depth_runs)"""
     _fields_ = [("start", C.c_uint32), ("depth", C.c_uint32)]
@@ -151,7 +162,7 @@ class SimuOptions(C.Structure):
                 ("output_dir", C.c_char_p), ("repeat_sample", C.c_int32), ("host_haplotypes", C.c_int32), ("gzip", C.c_int32),
                 ("shard_contigs", C.c_int32), ("no_eof_block", C.c_int32), ("exchange", C.c_void_p), ("exchange_user", C.c_void_p),
                 ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32),
-                ("truth_errors", C.c_int32), ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
+                ("truth_tags", C.c_int32), ("truth_errors", C.c_int32), ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
 
 
 # simu_options.exchange: all-reduce(sum) of n doubles over the ranks, in place
@@ -175,6 +186,7 @@ class SimuStats(C.Structure):
                 ("emit_clean_cap", C.c_uint32),
                 ("truth_records", C.c_uint64), ("truth_unmapped", C.c_uint64), ("truth_bytes", C.c_uint64),
                 ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double),
+                ("truth_tag_bytes", C.c_uint64), ("truth_md_dropped", C.c_uint64), ("truth_nm_sum", C.c_uint64), ("truth_xe_sum", C.c_uint64),
                 ("errors_bases", C.c_uint64), ("errors_subst", C.c_uint64), ("t_errors", C.c_double),
                 ("variant_rows", C.c_uint64), ("variant_dropped", C.c_uint64), ("variant_hits", C.c_uint64), ("t_variants", C.c_double),
                 ("depth_bases", C.c_uint64), ("depth_rows", C.c_uint64), ("t_depth", C.c_double)]
@@ -278,6 +290,11 @@ def load_engine():
     lib.sg_truth_bam.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.sg_fetch_truth.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
     lib.sg_truth_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.sg_truth_bam_tags.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.sg_truth_tag_info.argtypes = [vp, C.POINTER(SgTruthTagCounts)]
+    lib.sg_truth_tags.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint32,
+                                  C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                  C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
     lib.sg_depth_begin.argtypes = [vp, u64p, C.c_uint32]
     lib.sg_depth_add.argtypes = [vp, u64p]
@@ -529,6 +546,25 @@ def variants_format(contigs, populations, rows, counts=None, want_table: bool = 
     return res
 
 
+def truth_tags(cigar, seq: bytes, ref_codes: bytes, md_cap: int = 2048, tmpl_codes=None, reverse: bool = False, events=(), read: bytes = b""):
+    """sg_truth_tags (host only, no GPU): the tags of one truth BAM record.  `cigar`: len << 4 | op words (empty: an unmapped
+    record), `seq`: SEQ in BAM orientation, `ref_codes`: the contig's base codes from POS on; `tmpl_codes`: the template's
+    chain codes in chain direction (None: the template does not lie in its chain), `events`: ev_pack words in read
+    direction, `read`: the read in FASTQ orientation.  Returns (present, NM, MD text or None, XE or None)."""
+    lib = load_engine()
+    ops = (C.c_uint32 * max(len(cigar), 1))(*[int(v) for v in cigar])
+    ev = (C.c_uint32 * max(len(events), 1))(*[int(e) for e in events])
+    present, nm, md_len, xe = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    md = C.create_string_buffer(max(md_cap, 1))
+    rc = lib.sg_truth_tags(ops, len(cigar), bytes(seq), len(seq), bytes(ref_codes), len(ref_codes), md_cap,
+                           None if tmpl_codes is None else bytes(tmpl_codes), 0 if tmpl_codes is None else len(tmpl_codes), 1 if reverse else 0,
+                           ev, len(events), bytes(read), len(read), C.byref(present), C.byref(nm), md, C.byref(md_len), C.byref(xe))
+    if rc != 0:
+        raise SimuError(f"sg_truth_tags refused the record (code {rc})")
+    p = present.value
+    return p, (nm.value if p & TAG_NM else None), (md.raw[:md_len.value] if p & TAG_MD else None), (xe.value if p & TAG_XE else None)
+
+
 def errors_cells(cycles: int, n_qual: int, tmpl_len: int) -> int:
     """Cells of the true error counts' flat table (sg_errtab_counts): Q [2][cycles][n_qual][4] (bases, errors, other,
     inserted) | S [2][4][5] (from A C T G, to A C T G N) | I [2][L][2] | D [2][L][2] (events, bases)."""
@@ -661,11 +697,19 @@ class Session:
         self._sg(self.eng.sg_truth_reads(self.ctx, mate, first_slot, n, arr), "sg_truth_reads")
         return arr
 
-    def truth_bam(self):
-        """Build the pass's BAM records and their BGZF members on the device; returns (record bytes, BGZF bytes)."""
+    def truth_bam(self, tags: int = 0):
+        """Build the pass's BAM records and their BGZF members on the device; returns (record bytes, BGZF bytes).  `tags`: a
+        mask of TAG_NM | TAG_MD | TAG_XE, the optional fields the records carry (0: none, the records of sg_truth_bam)."""
         a, b = C.c_uint64(), C.c_uint64()
-        self._sg(self.eng.sg_truth_bam(self.ctx, C.byref(a), C.byref(b)), "sg_truth_bam")
+        self._sg(self.eng.sg_truth_bam_tags(self.ctx, int(tags), C.byref(a), C.byref(b)), "sg_truth_bam_tags")
         return a.value, b.value
+
+    def truth_tag_info(self):
+        """sg_truth_tag_counts of the last truth_bam(): records with each tag, the sums of NM and XE, MD texts dropped, tag
+        bytes, and the longest MD text a record carries."""
+        out = SgTruthTagCounts()
+        self._sg(self.eng.sg_truth_tag_info(self.ctx, C.byref(out)), "sg_truth_tag_info")
+        return out
 
     def fetch_truth(self, compressed: bool, nbytes: int, offset: int = 0) -> bytes:
         buf = C.create_string_buffer(max(nbytes, 1))

@@ -2,6 +2,7 @@
 // Same positional argument, usage text and exit codes; optional flags are additive:
 //   --seed N  --device D  --out DIR  --no-write [--fetch]  --quiet  --rank R --world W  --stats  --host-haplotypes  --gzip
 //   --truth-bam   every read's true alignment as <stem>.truth.bam beside the FASTQ files (simulate.h)
+//   --truth-tags  with --truth-bam: NM, MD and XE tags on its records (XE: the read's true sequencing errors against its haplotype)
 //   --truth-depth BIN   the reads' true coverage as <stem>.truth.depth.bedgraph (BIN 1: runs of equal depth; BIN > 1: means)
 //   --truth-variants    per variant of the variation and SNP files the reads that cover the site and those that carry the
 //                       allele, as <stem>.truth.variants.tsv
@@ -232,6 +233,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--host-haplotypes") opt.host_haplotypes = 1;
     else if (a == "--gzip") opt.gzip = 1;
     else if (a == "--truth-bam") opt.truth_bam = 1;
+    else if (a == "--truth-tags") opt.truth_tags = 1;
     else if (a == "--truth-depth") {
       const char* v = val();
       char* end = nullptr;
@@ -298,7 +300,7 @@ int main(int argc, char* argv[]) {
     fprintf(stderr,
             "stats: reads=%llu fragments=%llu bytes=%llu windows=%llu segments=%llu batches=%llu | load %.3fs (engine %.3fs reference %.3fs) haplotypes %.3fs "
             "plan %.3fs sample %.3fs (haplotype calls %.3fs sg_plan %.3fs) fetch %.3fs write %.3fs total %.3fs | kernels ms: plan %.3f namebase %.3f indel %.3f scan %.3f emit %.3f emit_slow %.3f | queued_items=%llu requeued_batches=%llu emit_kernel=%d slow_rows_lds=%d emit_lds=%u clean_cap=%u | compress %.3fs gz_bytes=%llu | "
-            "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f | "
+            "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f truth_tag_bytes=%llu truth_md_dropped=%llu truth_nm_sum=%llu truth_xe_sum=%llu | "
             "variant_rows=%llu variant_dropped=%llu variant_hits=%llu variants_s=%.3f | "
             "depth_bases=%llu depth_rows=%llu depth_s=%.3f | "
             "errors_bases=%llu errors_subst=%llu errors_s=%.3f\n",
@@ -310,6 +312,7 @@ int main(int argc, char* argv[]) {
             (unsigned long long)st.requeued_batches, st.emit_kernel, st.emit_slow_rows_lds, st.emit_lds_bytes,
             st.emit_clean_cap, st.t_compress, (unsigned long long)st.gz_bytes, (unsigned long long)st.truth_records,
             (unsigned long long)st.truth_unmapped, (unsigned long long)st.truth_bytes, (unsigned long long)st.truth_bgzf_bytes, st.t_truth,
+            (unsigned long long)st.truth_tag_bytes, (unsigned long long)st.truth_md_dropped, (unsigned long long)st.truth_nm_sum, (unsigned long long)st.truth_xe_sum,
             (unsigned long long)st.variant_rows, (unsigned long long)st.variant_dropped, (unsigned long long)st.variant_hits, st.t_variants,
             (unsigned long long)st.depth_bases, (unsigned long long)st.depth_rows, st.t_depth,
             (unsigned long long)st.errors_bases, (unsigned long long)st.errors_subst, st.t_errors);

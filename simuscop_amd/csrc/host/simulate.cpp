@@ -145,7 +145,17 @@ struct Driver {
   void truth_piece(Sink& sink) {
     auto t0 = Clock::now();
     uint64_t rb = 0, gb = 0, nrec = 0, nun = 0;
-    eng.check(sg_truth_bam(eng.ctx, &rb, &gb), "sg_truth_bam");
+    if (opt.truth_tags) {
+      eng.check(sg_truth_bam_tags(eng.ctx, SG_TAG_NM | SG_TAG_MD | SG_TAG_XE, &rb, &gb), "sg_truth_bam_tags");
+      sg_truth_tag_counts tc;
+      eng.check(sg_truth_tag_info(eng.ctx, &tc), "sg_truth_tag_info");
+      st.truth_tag_bytes += tc.tag_bytes;
+      st.truth_md_dropped += tc.md_dropped;
+      st.truth_nm_sum += tc.nm_sum;
+      st.truth_xe_sum += tc.xe_sum;
+    } else {
+      eng.check(sg_truth_bam(eng.ctx, &rb, &gb), "sg_truth_bam");
+    }
     eng.check(sg_truth_info(eng.ctx, &nrec, &nun), "sg_truth_info");
     st.truth_records += nrec;
     st.truth_unmapped += nun;

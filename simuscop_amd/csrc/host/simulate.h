@@ -43,6 +43,8 @@ typedef struct simu_options {
                            //    records are made and compressed on the device, piece by piece, in FASTQ order); needs the
                            //    device-assembled haplotypes (refused with host_haplotypes).  Sharded runs write parts like the
                            //    FASTQ parts: rank 0's carries the header, the last rank's the BGZF end-of-file block
+  int32_t truth_tags;      // 1: with truth_bam, its records carry NM, MD and XE tags (sg_truth_bam_tags; the rule: DESIGN.md "Truth
+                           //    tags"); refused without truth_bam
   int32_t truth_errors;    // 1: write per mate, cycle and reported quality how many bases were really wrong -- the read against the
                            //    haplotype bases it was cut from, so a variant allele is no error -- with a substitution matrix and
                            //    the sequencing indels to <stem>.truth.errors.tsv beside the FASTQ files (sg_errtab_*; the rule:
@@ -89,6 +91,10 @@ typedef struct simu_stats {
   uint64_t truth_bytes;    // ... bytes of the record stream and of its BGZF members (header and end-of-file block aside)
   uint64_t truth_bgzf_bytes;
   double t_truth;          // sg_truth_bam calls + fetching and writing their members (synchronous, per piece)
+  uint64_t truth_tag_bytes;   // truth_tags: bytes of truth_bytes that are tags, ...
+  uint64_t truth_md_dropped;  // ... mapped records left without MD (a text longer than the engine's cap), ...
+  uint64_t truth_nm_sum;      // ... and the sums of the NM and of the XE values
+  uint64_t truth_xe_sum;
   uint64_t errors_bases;   // truth_errors: read bases paired with an A/C/G/T template base, ...
   uint64_t errors_subst;   // ... of which the read shows another letter
   double t_errors;         // sg_errtab_* calls, formatting and writing the table
@@ -172,6 +178,7 @@ inline std::string simu_truth_refusal(const simu_options& o, bool sharded, bool 
   struct Rule { const char* flag; int32_t on; bool is_width, needs_map; const char* partial; };
   const Rule rules[] = {{"--truth-bam", o.truth_bam, false, true, nullptr}, {"--truth-depth", o.truth_depth, true, true, "depths"},
                         {"--truth-variants", o.truth_variants, false, true, "counts"}, {"--truth-errors", o.truth_errors, false, false, "tables"}};
+  if (o.truth_tags && !o.truth_bam) return "Error: --truth-tags needs --truth-bam: the tags go on the truth BAM's records";
   for (const Rule& r : rules) {
     if (all && r.is_width && r.on < 0) return std::string("Error: ") + r.flag + " needs a bin width of at least 1";
     if (all && r.on && r.needs_map && o.host_haplotypes)

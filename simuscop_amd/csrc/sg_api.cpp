@@ -1048,8 +1048,21 @@ int sg_truth_map(sg_ctx* ctx, const sg_hap_piece* pieces, const uint8_t* seg_fir
     chain_first[++chain] = n_pieces;
     at = 0;
   }
+  // the way back for the tag kernels: refID -> the codes of the first contig row that carries it
+  std::vector<sg::TagRef> refs;
+  for (size_t c = ctx->ref_contigs.size(); c-- > 0;) {
+    const int64_t ref = ref_ids ? (c < n_ref_ids ? ref_ids[c] : -1) : (int64_t)c;
+    if (ref < 0 || ref >= (int64_t)ctx->ref_contigs.size()) continue;   // (a refID no contig row can hold: its records fail the tagged call)
+    if (refs.size() <= (size_t)ref) refs.resize((size_t)ref + 1, sg::TagRef{0, 0});
+    refs[(size_t)ref] = sg::TagRef{ctx->ref_contigs[c].code_off, ctx->ref_contigs[c].length};
+  }
   T.mapped = false;   // (a copy that fails half-way leaves no map rather than a mixed one)
   ctx->pass.have_bam = false;   // (records of another map)
+  T.n_refs = 0;
+  if (!refs.empty()) {
+    SG_ENSURE(T.refs, refs.size() * sizeof(sg::TagRef));
+    SG_HIP(hipMemcpyAsync(T.refs.p, refs.data(), refs.size() * sizeof(sg::TagRef), hipMemcpyHostToDevice, ctx->stream));
+  }
   const size_t first_b = sg::truth_map_pieces_at(n_chains);
   SG_ENSURE(T.map, first_b + dev.size() * sizeof(sg::TruthPiece) + 64);
   SG_HIP(hipMemcpyAsync(T.map.p, chain_first.data(), (n_chains + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1058,6 +1071,7 @@ int sg_truth_map(sg_ctx* ctx, const sg_hap_piece* pieces, const uint8_t* seg_fir
   SG_HIP(hipStreamSynchronize(ctx->stream));   // dev is host memory of this frame
   T.sorted.swap(sorted);
   T.chain_first.swap(chain_first);
+  T.n_refs = (uint32_t)refs.size();
   T.mapped = true;
   return SG_OK;
 }
@@ -1089,24 +1103,38 @@ int sg_truth_reads(sg_ctx* ctx, int mate, uint32_t first_slot, uint32_t n, sg_tr
   return sg_read_back(ctx, out, ctx->truth.rows.p, (size_t)n * sizeof(sg::TruthReadRow));
 }
 
-int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
+static_assert(SG_TAG_NM == sg::kTagNM && SG_TAG_MD == sg::kTagMD && SG_TAG_XE == sg::kTagXE, "SG_TAG_* are the kernels' bits");
+
+int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) { return sg_truth_bam_tags(ctx, 0, record_bytes, bgzf_bytes); }
+
+// With tags == 0 exactly the kernels of the untagged stream are launched and nothing of the tags is allocated.
+int sg_truth_bam_tags(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
   if (!ctx) return SG_ERR_INVALID;
+  const char* const who = tags ? "sg_truth_bam_tags" : "sg_truth_bam";
+  if (tags & ~(uint32_t)(SG_TAG_NM | SG_TAG_MD | SG_TAG_XE)) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: tags is a mask of SG_TAG_NM, SG_TAG_MD and SG_TAG_XE");
   sg::TruthJob J;
   memset(&J, 0, sizeof J);
-  if (int rc = sg_pass_prelude(ctx, "sg_truth_bam", &J.map, true)) return rc;
+  if (int rc = sg_pass_prelude(ctx, who, &J.map, true)) return rc;
   sg_ctx::Truth& T = ctx->truth;
+  if ((tags & (SG_TAG_NM | SG_TAG_MD)) && (!T.n_refs || !ctx->ref_codes.p))
+    return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: NM and MD need the reference's codes (sg_reference_commit)");
+  if (tags && (uint32_t)ctx->P.L > sg::kTruthTagMaxL)
+    return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam_tags: reads too long for the tagged record kernel (templates of more than " +
+                                             std::to_string(sg::kTruthTagMaxL) + " bases)");
   sg_ctx::Pass& Q = ctx->pass;
   const sg::DevBatch& B = ctx->B;
   const uint32_t N = J.map.n_reads;
   Q.have_bam = false;
   Q.bam_rec_bytes = Q.bam_gz_bytes = Q.bam_records = Q.bam_unmapped = 0;
+  for (uint64_t& v : Q.bam_tags) v = 0;
   hipStream_t s = ctx->stream;
   // the pack kernel's stages: one record's FASTQ text and one record's image, for reads of up to L + 512 bases
   const uint32_t np_cap = (uint32_t)ctx->P.L + 512u;
   J.text_lds = (16u + 256u + 2u * np_cap + 4u + 31u) & ~15u;
-  J.image_lds = (16u + 36u + 256u + 4u * sg::kTruthMaxOps + np_cap + (np_cap + 1u) / 2u + 15u) & ~15u;
+  const uint32_t tag_cap = tags ? sg::truth_tag_bytes(tags, sg::kTruthMaxMd) : 0u;
+  J.image_lds = (16u + 36u + 256u + 4u * sg::kTruthMaxOps + np_cap + (np_cap + 1u) / 2u + tag_cap + 15u) & ~15u;
   if ((size_t)sg::kTruthWaveOps * 4 + 64 * 9 * 4 + J.text_lds + J.image_lds > 160u * 1024u)
-    return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: reads too long for the record kernel");
+    return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": reads too long for the record kernel");
   // work buffer: counters (8 u64: records, unmapped, flags, -, stream bytes) | rows | rec_len | rec_off | block sums
   const size_t off_rows = 64, off_len = off_rows + (size_t)N * sizeof(sg::TruthRow);
   const size_t off_off = (off_len + (size_t)N * 4 + 63) & ~(size_t)63, off_bsum = off_off + (size_t)N * 8;
@@ -1116,25 +1144,49 @@ int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
   J.rows = (sg::TruthRow*)(wk + off_rows);
   J.rec_len = (uint32_t*)(wk + off_len);
   J.rec_off = (const uint64_t*)(wk + off_off);
+  // the tags' job: per-read rows {NM, XE, MD length} and behind them the sizing kernel's eight counters
+  sg::TagJob G;
+  memset(&G, 0, sizeof G);
+  if (tags) {
+    const size_t at = sg_counters_at((size_t)N * sizeof(sg::TagRow));
+    SG_ENSURE(T.tag_rows, at + 64);
+    G.tags = tags;
+    G.n_refs = T.n_refs;
+    G.refs = T.refs.as<sg::TagRef>();
+    G.ref_codes = ctx->ref_codes.as<uint8_t>();
+    G.rows = T.tag_rows.as<sg::TagRow>();
+    G.counters = (unsigned long long*)(T.tag_rows.as<uint8_t>() + at);
+    SG_HIP(hipMemsetAsync(G.counters, 0, 64, s));
+  }
   uint64_t c[8] = {};
   if (int rc = sg_run_counted(ctx, wk, 8, c, [&]() {
         if (!N) return;
         sg::launch_truth_size(ctx->P, B, J, s);
+        if (tags) sg::launch_truth_tag_size(ctx->P, B, J, G, s);
         sg::launch_scan_u32(J.rec_len, N, (uint64_t*)(wk + off_bsum), (uint64_t*)(wk + off_off), (uint64_t*)(wk + 32), s);
       }))
     return rc;
-  if (c[2] & 3) return ctx->fail(SG_ERR_OVERFLOW, "sg_truth_bam: an alignment with more than " + std::to_string(sg::kTruthMaxOps) + " operations");
+  if (c[2] & 3) return ctx->fail(SG_ERR_OVERFLOW, std::string(who) + ": an alignment with more than " + std::to_string(sg::kTruthMaxOps) + " operations");
+  uint64_t tc[8] = {};
+  if (tags) {
+    if (int rc = sg_read_back(ctx, tc, G.counters, 64)) return rc;
+    if (tc[7] & 1) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: a read whose events or operations do not end at its length");
+    if (tc[7] & 2) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: an alignment outside its contig of the committed reference");
+    if (tc[7] & 4) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: a record outside its mate's text");
+  }
   const uint64_t total = c[4];
   if (total) {
     SG_ENSURE(T.rec, total + 64);
     J.out = T.rec.as<uint8_t>();
     J.out_bytes = total;
-    sg::launch_truth_pack(ctx->P, B, J, s);
+    if (tags) sg::launch_truth_pack_tags(ctx->P, B, J, G, s);
+    else sg::launch_truth_pack(ctx->P, B, J, s);
     uint64_t flags = 0;
     if (int rc = sg_read_back(ctx, &flags, wk + 16, 8)) return rc;
-    if (flags & 4) return ctx->fail(SG_ERR_UNSUPPORTED, "sg_truth_bam: a record does not fit the record kernel's stages");
-    if (int rc = deflate_text(ctx, T.rec.as<uint8_t>(), total, T.gz, &Q.bam_gz_bytes, "sg_truth_bam")) return rc;
+    if (flags & 4) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": a record does not fit the record kernel's stages");
+    if (int rc = deflate_text(ctx, T.rec.as<uint8_t>(), total, T.gz, &Q.bam_gz_bytes, who)) return rc;
   }
+  for (int i = 0; i < 7; i++) Q.bam_tags[i] = tc[i];
   Q.bam_rec_bytes = total;
   Q.bam_records = c[0];
   Q.bam_unmapped = c[1];
@@ -1155,6 +1207,15 @@ int sg_fetch_truth(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes,
     SG_HIP(hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP(hipStreamSynchronize(ctx->stream));
   }
+  return SG_OK;
+}
+
+int sg_truth_tag_info(sg_ctx* ctx, sg_truth_tag_counts* out) {
+  if (!ctx || !out) return SG_ERR_INVALID;
+  if (int rc = truth_need_map(ctx, "sg_truth_tag_info")) return rc;
+  if (!ctx->pass.have_bam) return ctx->fail(SG_ERR_INVALID, "sg_truth_tag_info: call sg_truth_bam first");
+  const uint64_t* t = ctx->pass.bam_tags;
+  *out = sg_truth_tag_counts{t[0], t[1], t[2], t[3], t[4], t[5], t[6], sg::kTruthMaxMd};
   return SG_OK;
 }
 

@@ -70,9 +70,10 @@ struct sg_ctx {
     bool from_build = false, mapped = false;
     std::vector<sg_truth_piece> sorted;
     std::vector<uint64_t> chain_first;
+    uint32_t n_refs = 0;   // the tag kernels' way from a refID back to its contig's codes: rows of `refs` (0: no reference codes)
   };
   struct Truth : TruthInfo {
-    DevBuf map, work, rec, gz, rows;
+    DevBuf map, work, rec, gz, rows, refs, tag_rows;
     void forget() { static_cast<TruthInfo&>(*this) = TruthInfo(); }
   } truth;
   // true coverage (sg_depth_*, sg_api_depth.cpp): the contigs' lengths and first slots in `diff`, the flat int32
@@ -159,6 +160,7 @@ struct sg_ctx {
     uint64_t gz_bytes[2] = {0, 0};
     bool have_bam = false;            // sg_truth_bam: truth.rec / truth.gz hold the pass's records
     uint64_t bam_rec_bytes = 0, bam_gz_bytes = 0, bam_records = 0, bam_unmapped = 0;
+    uint64_t bam_tags[7] = {0, 0, 0, 0, 0, 0, 0};   // sg_truth_bam_tags: records with NM, MD, XE, the sums of NM and XE, MD texts dropped, tag bytes
   } pass;
 
   bool profiling = false;

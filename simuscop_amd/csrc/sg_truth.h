@@ -456,4 +456,113 @@ constexpr uint32_t kErrLdsBudget = 72u * 1024u;   // two workgroups a CU
 uint32_t errtab_win_cycles(const ErrtabDims& d);
 void launch_errtab_add(const DevProfile& P, const DevBatch& B, const ErrtabJob& J, uint32_t n_cus, hipStream_t s);
 
+// ---- NM, MD and XE tags of the truth BAM records (simuReads --truth-tags; kernels: sg_truth_tags.hip, sg_truth.hip) ----
+// The rule (DESIGN.md "Truth tags").  NM and MD are a function of the record's own fields and the reference: POS, the
+// operations, SEQ in BAM orientation and the contig's base codes.  XE is the read in FASTQ orientation against its
+// template, laid out by errtab_walk.
+enum : uint32_t { kTagNM = 1u, kTagMD = 2u, kTagXE = 4u };   // SG_TAG_*
+// The longest MD text a record carries.  Without a variant deletion a text has at most 2 * L + 2 * (D runs) + 1 bytes
+// (DESIGN.md derives it), and an alignment has at most kTruthMaxOps / 2 D runs: templates of up to kTruthTagMaxL bases
+// never reach the cap, and the tagged call refuses longer ones.
+constexpr uint32_t kTruthMaxMd = 2048;
+constexpr uint32_t kTruthTagMaxL = (kTruthMaxMd - kTruthMaxOps - 1u) / 2u;
+constexpr uint32_t kMdDropped = 0xFFFFFFFFu;
+// the reference letter of a base code: the codes keep no IUPAC letter, so all but A C T G come out as N
+__host__ __device__ inline uint32_t truth_ref_letter(uint32_t code) { return code == 0u ? 'A' : code == 1u ? 'C' : code == 2u ? 'T' : code == 3u ? 'G' : 'N'; }
+// a SEQ letter matches iff it is the reference letter and one of A, C, G, T (an N never matches: calmd's rule)
+__host__ __device__ inline bool truth_base_matches(uint32_t seq_letter, uint32_t code) { return code < 4u && seq_letter == truth_ref_letter(code); }
+// a FASTQ letter as SEQ shows it in a record that is turned round
+__host__ __device__ inline uint32_t truth_complement(uint32_t ch) { return ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch; }
+__host__ __device__ inline uint32_t truth_digits(uint32_t v) {
+  uint32_t n = 1;
+  while (v >= 10u) { v /= 10u; n++; }
+  return n;
+}
+// digit `i` (0: the leading one) of v, which has n digits
+__host__ __device__ inline uint32_t truth_digit(uint32_t v, uint32_t n, uint32_t i) {
+  for (uint32_t k = i + 1u; k < n; k++) v /= 10u;
+  return '0' + v % 10u;
+}
+// bytes of a record's tags: `present` says which it gets, md_len is its MD text's length
+__host__ __device__ inline uint32_t truth_tag_bytes(uint32_t present, uint32_t md_len) {
+  return ((present & kTagNM) ? 7u : 0u) + ((present & kTagXE) ? 7u : 0u) + ((present & kTagMD) ? 3u + md_len + 1u : 0u);
+}
+
+struct TagWalk {
+  uint32_t nm, md_len;   // md_len counts every byte of the text, written or not
+  uint32_t q_end;        // SEQ letters the operations cover
+  uint64_t r_end;        // reference bases from POS on they cover
+};
+// NM and MD of one record, base by base.  `ops` are its operations (len << 4 | op), seq(i) is SEQ letter i in BAM
+// orientation, ref(x) the base code x bases behind POS; put(o, ch) gets byte o of the MD text.
+template <class Seq, class Ref, class Put>
+__host__ __device__ inline TagWalk truth_tags_walk(const uint32_t* ops, uint32_t n_ops, Seq seq, Ref ref, Put put) {
+  TagWalk W = {0u, 0u, 0u, 0u};
+  uint32_t m = 0;
+  auto number = [&]() {
+    const uint32_t n = truth_digits(m);
+    for (uint32_t i = 0; i < n; i++) put(W.md_len++, truth_digit(m, n, i));
+    m = 0;
+  };
+  for (uint32_t k = 0; k < n_ops; k++) {
+    const uint32_t len = ops[k] >> 4, op = ops[k] & 15u;
+    if (op == kOpM) {
+      for (uint32_t i = 0; i < len; i++) {
+        const uint32_t code = ref(W.r_end + i);
+        if (truth_base_matches(seq(W.q_end + i), code)) { m++; continue; }
+        number();
+        put(W.md_len++, truth_ref_letter(code));
+        W.nm++;
+      }
+      W.q_end += len;
+      W.r_end += len;
+    } else if (op == kOpD) {
+      number();
+      put(W.md_len++, (uint32_t)'^');
+      for (uint32_t i = 0; i < len; i++) put(W.md_len++, truth_ref_letter(ref(W.r_end + i)));
+      W.nm += len;
+      W.r_end += len;
+    } else if (op == kOpN) {
+      W.r_end += len;
+    } else {   // I, S
+      if (op == kOpI) W.nm += len;
+      W.q_end += len;
+    }
+  }
+  number();
+  return W;
+}
+// XE of one read: tmpl(j) is the chain's base code of T'[j] as the read sees it (errtab_tmpl_code), read(r) letter r of
+// the read in FASTQ orientation.  kErrWalkBad: the events do not end at `np`.
+template <class Tmpl, class Read>
+__host__ __device__ inline uint32_t truth_xe(const uint32_t* events, uint32_t n_events, uint32_t L, uint32_t np, Tmpl tmpl, Read read) {
+  if (errtab_walk(events, n_events, L, [](uint32_t, uint32_t, uint32_t, uint32_t) {}) != np) return kErrWalkBad;
+  uint32_t xe = 0;
+  errtab_walk(events, n_events, L, [&](uint32_t kind, uint32_t j, uint32_t r, uint32_t n) {
+    if (kind != 0u) { xe += n; return; }
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t tc = tmpl(j + i);
+      if (tc < 4u && errtab_read_code(read(r + i)) != tc) xe++;
+    }
+  });
+  return xe;
+}
+
+// Per read, in record order: what truth_tag_size_kernel found (md_len = kMdDropped: the text is longer than kTruthMaxMd)
+struct TagRow { uint32_t nm, xe, md_len; };
+// refID -> its contig's codes (the first row of the committed reference with that refID)
+struct TagRef { uint64_t code_off, length; };
+struct TagJob {
+  uint32_t tags;                 // kTag*
+  uint32_t n_refs;
+  const TagRef* refs;            // [n_refs]
+  const uint8_t* ref_codes;
+  TagRow* rows;                  // [n_reads]
+  unsigned long long* counters;  // [0..2] records with NM, MD, XE, [3] sum of NM, [4] of XE, [5] MD texts dropped, [6] tag bytes,
+                                 // [7] flags: 1 a walk that does not end at the read's length, 2 a reference span past its contig's end,
+                                 //            4 a record outside its mate's text
+};
+void launch_truth_tag_size(const DevProfile& P, const DevBatch& B, const TruthJob& J, const TagJob& T, hipStream_t s);
+void launch_truth_pack_tags(const DevProfile& P, const DevBatch& B, const TruthJob& J, const TagJob& T, hipStream_t s);
+
 }  // namespace sg

@@ -13,8 +13,12 @@
 //                       4-bit bases, qualities; turned round for a reverse read), and leaves as 16-byte pieces --
 //                       records are ~300 unaligned bytes, stored by their own lanes every store instruction would
 //                       touch 64 cache lines (the reason indel_kernel's rows leave through LDS); only the bytes an
-//                       image shares a 16-byte piece with its neighbours' go out singly.
-#include "sg_truth.h"
+//                       image shares a 16-byte piece with its neighbours' go out singly.  truth_pack_kernel<true>
+//                       (simuReads --truth-tags) appends the NM, XE and MD tags that truth_tag_size_kernel
+//                       (sg_truth_tags.hip) has sized; truth_pack_kernel<false> is the kernel without them.
+#include <type_traits>
+
+#include "sg_truth_tags.h"
 
 namespace sg {
 namespace {
@@ -67,7 +71,12 @@ __device__ __forceinline__ uint32_t nt16(uint32_t ch, bool comp) {
   return c == 1u ? 8u : c == 8u ? 1u : c == 2u ? 4u : 2u;
 }
 
-__global__ __launch_bounds__(64) void truth_pack_kernel(DevProfile P, DevBatch B, TruthJob J) {
+// The record kernel.  kTags = false is the kernel as it has always been, its own instantiation with nothing of the tags
+// in it (a body shared through a wrapper comes out with other register counts); kTags = true appends the record's tags
+// behind the qualities (T: the job of truth_tag_size_kernel, whose rows say what each record gets).
+struct NoTagJob {};
+template <bool kTags>
+__global__ __launch_bounds__(64) void truth_pack_kernel(DevProfile P, DevBatch B, TruthJob J, std::conditional_t<kTags, TagJob, NoTagJob> T) {
   extern __shared__ uint4 lds16[];
   uint32_t* const cig = (uint32_t*)lds16;                       // [kTruthWaveOps]
   uint32_t* const fix = cig + kTruthWaveOps;                    // [64][9] the records' fixed words
@@ -93,6 +102,10 @@ __global__ __launch_bounds__(64) void truth_pack_kernel(DevProfile P, DevBatch B
     }
   }
   const bool live = rec_len != 0u && g.live;
+  TagRow tag = {0u, 0u, 0u};
+  if constexpr (kTags) {
+    if (live) tag = T.rows[idx];
+  }
   uint32_t cig_base = row.n_ops;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -170,7 +183,17 @@ __global__ __launch_bounds__(64) void truth_pack_kernel(DevProfile P, DevBatch B
     const uint32_t lq = qname_len(B, r_hdr), seq_b = (r_np + 1u) / 2u;
     const uint32_t o_cig = 36u + lq + 1u, o_seq = o_cig + 4u * r_ops, o_qual = o_seq + seq_b;
     const uint8_t* tx = text + dt;
-    for (uint32_t k = lane; k < r_len; k += 64u) {
+    const uint32_t img_len = kTags ? o_qual + r_np : r_len;   // the record without its tags
+    uint32_t present = 0u, r_md = 0u;
+    if constexpr (kTags) {
+      r_md = __shfl(tag.md_len, r, 64);
+      present = tags_present(T.tags, r_ops != 0u, __shfl((uint32_t)g.inside, r, 64) != 0u, r_md);
+      if (img_len + truth_tag_bytes(present, r_md) != r_len) {   // (the sizing kernel's row and this record disagree: nothing is written)
+        if (lane == 0u) atomicOr(&J.counters[2], 4ull);
+        continue;
+      }
+    }
+    for (uint32_t k = lane; k < img_len; k += 64u) {
       uint32_t b;
       if (k < 36u) {
         b = fix[r * 9u + (k >> 2)] >> (8u * (k & 3u));
@@ -188,6 +211,28 @@ __global__ __launch_bounds__(64) void truth_pack_kernel(DevProfile P, DevBatch B
         b = tx[r_hdr + r_np + 3u + (flip ? r_np - 1u - i : i)] - 33u;
       }
       image[h + k] = (uint8_t)b;
+    }
+    if constexpr (kTags) {   // NM:I, XE:I, MD:Z behind the qualities
+      const uint32_t r_nm = __shfl(tag.nm, r, 64), r_xe = __shfl(tag.xe, r, 64);
+      uint8_t* tp = image + h + img_len;
+      if (present & kTagNM) {
+        if (lane < 7u) tp[lane] = (uint8_t)(lane == 0u ? 'N' : lane == 1u ? 'M' : lane == 2u ? 'I' : r_nm >> (8u * (lane - 3u)));
+        tp += 7;
+      }
+      if (present & kTagXE) {
+        if (lane < 7u) tp[lane] = (uint8_t)(lane == 0u ? 'X' : lane == 1u ? 'E' : lane == 2u ? 'I' : r_xe >> (8u * (lane - 3u)));
+        tp += 7;
+      }
+      if (present & kTagMD) {
+        if (lane < 3u) tp[lane] = (uint8_t)(lane == 0u ? 'M' : lane == 1u ? 'D' : 'Z');
+        if (lane == 3u) tp[3u + r_md] = 0u;
+        const uint32_t ref = fix[r * 9u + 1u], pos = fix[r * 9u + 2u];
+        const uint64_t len = ref < T.n_refs ? T.refs[ref].length : 0ull;
+        if (pos <= len) {   // (the sizing kernel has checked the span; a record it refused fails the call)
+          const WaveSeq S = {tx + r_hdr, r_np, flip};
+          wave_tags_walk<true>(cig + r_cig, r_ops, S, T.ref_codes + T.refs[ref].code_off + pos, len - pos, lane, tp + 3, r_md);
+        }
+      }
     }
     wave_lds_sync();
     uint8_t* const dst = J.out + (r_off - h);   // 16-byte aligned: the stream's buffer is, and r_off - h is a multiple of 16
@@ -229,8 +274,14 @@ void launch_truth_size(const DevProfile& P, const DevBatch& B, const TruthJob& J
 void launch_truth_pack(const DevProfile& P, const DevBatch& B, const TruthJob& J, hipStream_t s) {
   if (!J.map.n_reads) return;
   const size_t lds = (size_t)kTruthWaveOps * 4 + 64 * 9 * 4 + J.text_lds + J.image_lds;
-  (void)hipFuncSetAttribute((const void*)truth_pack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(truth_pack_kernel, dim3((J.map.n_reads + 63u) / 64u), dim3(64), lds, s, P, B, J);
+  (void)hipFuncSetAttribute((const void*)truth_pack_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(truth_pack_kernel<false>, dim3((J.map.n_reads + 63u) / 64u), dim3(64), lds, s, P, B, J, NoTagJob{});
+}
+void launch_truth_pack_tags(const DevProfile& P, const DevBatch& B, const TruthJob& J, const TagJob& T, hipStream_t s) {
+  if (!J.map.n_reads) return;
+  const size_t lds = (size_t)kTruthWaveOps * 4 + 64 * 9 * 4 + J.text_lds + J.image_lds;
+  (void)hipFuncSetAttribute((const void*)truth_pack_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(truth_pack_kernel<true>, dim3((J.map.n_reads + 63u) / 64u), dim3(64), lds, s, P, B, J, T);
 }
 void launch_truth_reads(const DevProfile& P, const DevBatch& B, uint32_t mate, uint32_t first_slot, uint32_t n, TruthReadRow* out, hipStream_t s) {
   if (!n) return;
