@@ -720,6 +720,7 @@ int sg_load_prepared_profile(sg_ctx* ctx, const sg_profile_tables* Tp) {
   }
   ctx->have_profile = true;
   retire_plan(ctx);
+  if (sg::emit_variant(P) != 0) sg::preload_emit_fast();   // (not inside the first pass's timed launch)
   return SG_OK;
 }
 

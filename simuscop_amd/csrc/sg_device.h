@@ -98,7 +98,7 @@ struct DevBatch {
                                 // (sums by indel_kernel, scanned in place by block_base_kernel; the segments' own bases: totals + kTotalsSegBase)
   uint32_t seg_shift;
   uint4* meta;                  // [2][n_slots][3] per-read 48-byte rows for the emit kernels: m0, m1, name text (indel_kernel)
-  // (from byte 128 on: the emit kernels' read-group counters, one 128-byte line each, see GroupRuns in sg_kernels.hip)
+  // (from byte 128 on: the emit kernels' read-group counters, one 128-byte line each, see GroupRuns in sg_emit.h)
   uint64_t* totals;             // [0],[1] bytes per mate; [2] fragments produced; [3] flags (1 events, 2 slow queue full); [4] slow-queue counts;
   uint2* slowq;                 // [2][slowq_cap] (slot, item) left to emit_slow_kernel by the fast emit kernel
   uint32_t* slowq_count;        // [2] entries appended per mate (may exceed slowq_cap: overflow)
@@ -107,7 +107,7 @@ struct DevBatch {
   uint64_t out_cap[2];
 };
 
-// ---- launchers of the sampling pass (sg_kernels.hip); the window planner's are in sg_windows.h, the scan's in sg_scan.h ----
+// ---- launchers of the sampling pass (sg_kernels.hip; the straight-line kernel's own, launch_emit_fast, in sg_emit.h); the window planner's are in sg_windows.h, the scan's in sg_scan.h ----
 void launch_plan(const DevProfile& P, const DevBatch& B, hipStream_t s);
 void launch_namebase(const DevBatch& B, hipStream_t s);
 void launch_indel(const DevProfile& P, const DevBatch& B, hipStream_t s);
@@ -121,6 +121,7 @@ int emit_variant(const DevProfile& P);
 // the main kernel's dynamic LDS and the straight-line kernel's clean-item list
 struct EmitPath { int main_kernel; int slow_rows_lds; uint32_t lds_bytes, clean_cap; };
 EmitPath emit_path(const DevProfile& P, const DevBatch& B, bool force_generic);
+void preload_emit_fast();   // sg_emit_fast.hip: the straight-line kernel's device code onto the current device
 uint32_t record_seg_shift(uint32_t n_slots);
 void launch_encode(uint8_t* buf, size_t bytes, hipStream_t s);
 

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kErrThreads) void errtab_add_kernel(DevProfile P, D
       toff = text_offset(B, m, t);
       coff = B.chain_off[geo.chain] + geo.tmpl_off;
     }
-    const uint32_t packed = geo.np | (geo.nev << 16) | (geo.hdr << 22);   // 16 + 6 + 10 bits, as the meta row holds them
+    const uint32_t packed = row::pack_y(geo.np, geo.nev, geo.hdr);   // 16 + 6 + 10 bits, as the meta row holds them
     unsigned long long todo = __ballot(use);
     const unsigned long long outside = __ballot(geo.live && !geo.inside);
     if (first && lane == 0u) n_skipped += (uint32_t)__popcll(outside);
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kErrThreads) void errtab_add_kernel(DevProfile P, D
       const uint32_t pk = __shfl(packed, r, 64), rev = __shfl(geo.reverse, r, 64);
       const uint64_t r_toff = ((uint64_t)__shfl((uint32_t)(toff >> 32), r, 64) << 32) | __shfl((uint32_t)toff, r, 64);
       const uint64_t r_coff = ((uint64_t)__shfl((uint32_t)(coff >> 32), r, 64) << 32) | __shfl((uint32_t)coff, r, 64);
-      const uint32_t np = pk & 0xFFFFu, nev = (pk >> 16) & 63u, hdr = pk >> 22;
+      const uint32_t np = row::np(pk), nev = row::nev(pk), hdr = row::hdr_len(pk);
       const uint32_t* ev = B.events + ((size_t)m * B.n_slots + (g * 64u + r)) * SG_MAX_EVENTS;
       // the read as a whole: a read refused here counts nowhere (a quality byte outside the range refuses its base alone,
       // below; either way the call fails and the table is undefined until it is reset)

@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sg_device.h"
+#include "sg_emit.h"
 
 namespace sg {
 
@@ -165,17 +165,18 @@ struct ReadGeom {
 __device__ __forceinline__ ReadGeom read_geom(const DevProfile& P, const DevBatch& B, uint32_t t, uint32_t m) {
   ReadGeom g = {};
   const size_t idx = (size_t)m * B.n_slots + t;
-  const uint4 m1 = B.meta[idx * 3 + 1];
-  const uint32_t flen = m1.x & 0x3FFFFFFFu;
+  ReadRow rd;   // (sg_emit.h)
+  rd.m1 = B.meta[idx * 3 + 1];
+  const uint32_t flen = rd.flen();
   g.live = flen != 0u;
   if (!g.live) return g;
-  const uint4 m0 = B.meta[idx * 3];
-  const uint64_t foff = ((uint64_t)m0.y << 32) | m0.x;
+  rd.m0 = B.meta[idx * 3];
+  const uint64_t foff = rd.frag_off();
   const uint32_t L = (uint32_t)P.L;
-  g.reverse = m1.x >> 31;
-  g.np = m1.y & 0xFFFFu;
-  g.nev = (m1.y >> 16) & 63u;   // the row's count: indel_kernel drops the events of a read that would get shorter than 50
-  g.hdr = m1.y >> 22;
+  g.reverse = rd.rev() ? 1u : 0u;
+  g.np = rd.np();
+  g.nev = rd.nev();   // the row's count: indel_kernel drops the events of a read that would get shorter than 50
+  g.hdr = rd.hdr_len();
   g.chain = B.windows[B.pairs[t].win].chain;
   const uint64_t c0 = B.chain_off[g.chain], tmpl = g.reverse ? foff + flen - L : foff;
   g.inside = flen >= L && tmpl >= c0 && tmpl - c0 + L <= B.chain_len[g.chain];
@@ -184,13 +185,8 @@ __device__ __forceinline__ ReadGeom read_geom(const DevProfile& P, const DevBatc
   return g;
 }
 
-// rec_offset() of sg_kernels.hip: where read t's FASTQ record starts in its mate's text
-__device__ __forceinline__ uint64_t text_offset(const DevBatch& B, uint32_t m, uint32_t t) {
-  const uint32_t blk = t >> 8;
-  const uint64_t* segbase = (const uint64_t*)((const uint8_t*)B.totals + kTotalsSegBase);
-  return segbase[m * 16u + (blk >> B.seg_shift)] + B.blkbase[(size_t)m * ((B.n_slots + 255u) >> 8) + blk] +
-         B.recloc[(size_t)m * B.n_slots + t];
-}
+// where read t's FASTQ record starts in its mate's text
+__device__ __forceinline__ uint64_t text_offset(const DevBatch& B, uint32_t m, uint32_t t) { return rec_offset(B, m, t); }
 
 constexpr uint32_t kTruthMaxOps = 256;     // CIGAR operations of one record (more: SG_ERR_OVERFLOW)
 constexpr uint32_t kTruthWaveOps = 2048;   // ... and of the 64 records one wave packs

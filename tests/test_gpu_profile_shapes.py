@@ -3,7 +3,8 @@ byte for byte on profiles of tests/profile_shapes.py, whose rows all differ (an 
 changes bytes), with all-zero / one-hot / identity-less substitution rows and all-zero / single-symbol quality rows.
 
 The matrix holds a shape on each side of every boundary of the emit kernels' choice (sg_kernels.hip emit_lds /
-emit_path; EMIT_WAVES 16, META_ROW 32, 160 KiB of LDS): substitution rows go to LDS while 32 KiB + contexts x bins x 16 B
+emit_path, 160 KiB of LDS; EMIT_WAVES 16, META_ROW 32 and the straight-line kernel's layout, FastLds, in sg_emit.h):
+substitution rows go to LDS while 32 KiB + contexts x bins x 16 B
 fits; the straight-line kernel (k-mer 3 only) while its table image -- bins x (192 + 4 W) words, W the alias columns --
 and its queues fit, its deferred items then go to emit_slow_kernel<3, rows in LDS or not>.  Each row states the path it
 must take (the `--stats` line: sg_emit_path of the last pass), and straight-line rows must have queued items for
