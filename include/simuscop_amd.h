@@ -196,8 +196,8 @@ int sg_plan(sg_ctx* ctx, const sg_batch* batch);
  * keeps its text -- sg_result, sg_fetch, sg_fetch_range, sg_device_output, sg_compress,
  * sg_fetch_compressed, sg_detach_outputs, sg_emit_info and sg_emit_path go on working until the next
  * sg_plan / sg_sample -- but its rows are no longer those of the chains and the profile: the calls
- * that read them (sg_truth_reads, sg_truth_bam, sg_depth_add, sg_variants_add, sg_errtab_add) are
- * refused with SG_ERR_INVALID.                                                                    */
+ * that read them (sg_truth_reads, sg_truth_bam, sg_bamsort_pass, sg_depth_add, sg_variants_add,
+ * sg_errtab_add) are refused with SG_ERR_INVALID.                                                 */
 int sg_sample(sg_ctx* ctx);
 /* Wait for the pass and report sizes: FASTQ bytes for mate 1 / mate 2 (0 for SE) and the number
  * of fragments actually produced (pairs for PE, reads for SE).                                   */
@@ -427,6 +427,34 @@ int sg_truth_tag_info(sg_ctx* ctx, sg_truth_tag_counts* out);
 int sg_truth_tags(const uint32_t* cigar, uint32_t n_ops, const char* seq, uint32_t seq_len, const uint8_t* ref_codes, uint64_t n_ref,
                   uint32_t md_cap, const uint8_t* tmpl_codes, uint32_t tmpl_len, int reverse, const uint32_t* events, uint32_t n_events,
                   const char* read, uint32_t read_len, uint32_t* present, uint32_t* nm, char* md, uint32_t* md_len, uint32_t* xe);
+
+/* ---- the truth BAM in coordinate order (simuReads --truth-sort) -------------------------------------
+ * The order: key of a record = (refID as u32) << 32 | (POS as u32), from the record's own fields, so an unmapped read
+ * placed at its mate sorts at its mate's place and an unplaced one (-1 / -1) has the largest key and sorts last; ties
+ * keep the order of the unsorted stream (a stable sort).  The records themselves are the bytes of sg_truth_bam_tags.
+ * Opt-in: a context that never calls these launches no kernel of this part and holds no memory for it.
+ *   sg_bamsort_pass   sg_truth_bam_tags (same preconditions, limits and failures) with the record stream in key order and
+ *                     uncompressed: sizing kernels, keys of the live records, a stable radix sort on the device, offsets,
+ *                     then the record kernels unchanged.  *records = records made.  sg_truth_info and sg_truth_tag_info
+ *                     describe it; sg_fetch_truth reads its stream too (no members: bgzf bytes 0)
+ *   sg_bamsort_merge  n_runs slices in host memory, run r holding n[r] records of lens[r][i] bytes back to back in
+ *                     records[r] (record_bytes[r] in all) with keys[r][i]: uploads them in run order, sorts the
+ *                     concatenation stably by key, gathers the records and compresses the stream (BGZF members as
+ *                     sg_deflate_bgzf makes them, no EOF block).  Runs with ascending keys are what a merge expects, but
+ *                     any keys are sorted correctly; n_runs = 0 and empty runs are legal.  Needs no pass, no profile and
+ *                     no piece map, and disturbs none.  Fewer than 2^32 records; lengths that do not add up to
+ *                     record_bytes[r]: SG_ERR_INVALID.  The slices are the caller's again on return
+ *   sg_bamsort_index  keys and lengths, in output order, of the last sg_bamsort_pass or sg_bamsort_merge: *n = records;
+ *                     with both arrays NULL only that, else SG_ERR_OVERFLOW when cap < *n
+ *   sg_bamsort_fetch  bytes [offset, offset + bytes) of that call's record stream (compressed = 0) or of a merge's BGZF
+ *                     members (1; a pass has none: SG_ERR_INVALID)
+ * SG_BAMSORT_TILE: records one block of the sort takes (nothing a caller has to respect; the tests size their cases by it). */
+#define SG_BAMSORT_TILE 1024
+int sg_bamsort_pass(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64_t* records);
+int sg_bamsort_merge(sg_ctx* ctx, uint32_t n_runs, const void* const* records, const uint64_t* record_bytes, const uint64_t* const* keys,
+                     const uint32_t* const* lens, const uint64_t* n, uint64_t* out_bytes, uint64_t* bgzf_bytes);
+int sg_bamsort_index(sg_ctx* ctx, uint64_t* keys_out, uint32_t* lens_out, uint64_t cap, uint64_t* n);
+int sg_bamsort_fetch(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes, void* host_dst);
 
 /* ---- true coverage: the depth the reads of all passes really laid down (simuReads --truth-depth) -------------------
  * Coverage adds up, so it needs no sort: one int32 difference array over the reference (len + 1 slots per contig, 4

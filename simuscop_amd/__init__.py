@@ -33,6 +33,7 @@ ENGINE_SYMBOLS = [
     "sg_release_cached_memory",
     "sg_truth_align", "sg_truth_map", "sg_truth_pieces", "sg_truth_reads", "sg_truth_bam", "sg_fetch_truth", "sg_truth_info",
     "sg_truth_bam_tags", "sg_truth_tag_info", "sg_truth_tags",
+    "sg_bamsort_pass", "sg_bamsort_merge", "sg_bamsort_index", "sg_bamsort_fetch",
     "sg_depth_begin", "sg_depth_add", "sg_depth_add_spans", "sg_depth_bins", "sg_depth_runs", "sg_depth_fetch", "sg_depth_reset",
     "sg_depth_info", "sg_depth_end",
     "sg_variants_begin", "sg_variants_add", "sg_variants_counts", "sg_variants_reset", "sg_variants_info", "sg_variants_end",
@@ -162,7 +163,7 @@ class SimuOptions(C.Structure):
                 ("output_dir", C.c_char_p), ("repeat_sample", C.c_int32), ("host_haplotypes", C.c_int32), ("gzip", C.c_int32),
                 ("shard_contigs", C.c_int32), ("no_eof_block", C.c_int32), ("exchange", C.c_void_p), ("exchange_user", C.c_void_p),
                 ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32),
-                ("truth_tags", C.c_int32), ("truth_errors", C.c_int32), ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
+                ("truth_tags", C.c_int32), ("truth_sort", C.c_int32), ("truth_errors", C.c_int32), ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
 
 
 # simu_options.exchange: all-reduce(sum) of n doubles over the ranks, in place
@@ -187,6 +188,7 @@ class SimuStats(C.Structure):
                 ("truth_records", C.c_uint64), ("truth_unmapped", C.c_uint64), ("truth_bytes", C.c_uint64),
                 ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double),
                 ("truth_tag_bytes", C.c_uint64), ("truth_md_dropped", C.c_uint64), ("truth_nm_sum", C.c_uint64), ("truth_xe_sum", C.c_uint64),
+                ("truth_sort_runs", C.c_uint64), ("truth_sort_tiles", C.c_uint64), ("truth_spool_bytes", C.c_uint64), ("t_truth_sort", C.c_double),
                 ("errors_bases", C.c_uint64), ("errors_subst", C.c_uint64), ("t_errors", C.c_double),
                 ("variant_rows", C.c_uint64), ("variant_dropped", C.c_uint64), ("variant_hits", C.c_uint64), ("t_variants", C.c_double),
                 ("depth_bases", C.c_uint64), ("depth_rows", C.c_uint64), ("t_depth", C.c_double)]
@@ -296,6 +298,10 @@ def load_engine():
                                   C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    lib.sg_bamsort_pass.argtypes = [vp, C.c_uint32, u64p, u64p]
+    lib.sg_bamsort_merge.argtypes = [vp, C.c_uint32, C.POINTER(vp), u64p, C.POINTER(u64p), C.POINTER(u32p), u64p, u64p, u64p]
+    lib.sg_bamsort_index.argtypes = [vp, u64p, u32p, C.c_uint64, u64p]
+    lib.sg_bamsort_fetch.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
     lib.sg_depth_begin.argtypes = [vp, u64p, C.c_uint32]
     lib.sg_depth_add.argtypes = [vp, u64p]
     lib.sg_depth_add_spans.argtypes = [vp, u32p, u64p, u64p, C.c_uint64]
@@ -367,6 +373,8 @@ def load_host():
     lib.simu_variant_table.argtypes = [vp, C.c_void_p, C.c_uint64, u64p, C.c_char_p, C.c_size_t]
     lib.simu_errors_format.argtypes = [u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, u64p]
     lib.simu_errors_format.restype = C.c_uint64
+    lib.simu_sort_tiles.argtypes = [C.c_uint32, C.POINTER(u64p), u64p, C.POINTER(u64p), C.c_uint64, u64p, C.POINTER(C.c_uint8), C.c_uint64]
+    lib.simu_sort_tiles.restype = C.c_uint64
     _host = lib
     return lib
 
@@ -565,6 +573,78 @@ def truth_tags(cigar, seq: bytes, ref_codes: bytes, md_cap: int = 2048, tmpl_cod
     return p, (nm.value if p & TAG_NM else None), (md.raw[:md_len.value] if p & TAG_MD else None), (xe.value if p & TAG_XE else None)
 
 
+BAMSORT_TILE = 1024   # SG_BAMSORT_TILE: records one block of the device sort takes
+
+
+def _bamsort_index(eng, ctx):
+    n = C.c_uint64()
+    rc = eng.sg_bamsort_index(ctx, None, None, 0, C.byref(n))
+    if rc != 0:
+        raise SimuError(f"sg_bamsort_index: {eng.sg_last_error(ctx).decode(errors='replace')}")
+    keys, lens = (C.c_uint64 * max(1, n.value))(), (C.c_uint32 * max(1, n.value))()
+    rc = eng.sg_bamsort_index(ctx, keys, lens, n.value, C.byref(n))
+    if rc != 0:
+        raise SimuError(f"sg_bamsort_index: {eng.sg_last_error(ctx).decode(errors='replace')}")
+    return list(keys[:n.value]), list(lens[:n.value])
+
+
+def _bamsort_fetch(eng, ctx, compressed: bool, nbytes: int, offset: int = 0) -> bytes:
+    buf = C.create_string_buffer(max(1, nbytes))
+    rc = eng.sg_bamsort_fetch(ctx, 1 if compressed else 0, offset, nbytes, buf)
+    if rc != 0:
+        raise SimuError(f"sg_bamsort_fetch: {eng.sg_last_error(ctx).decode(errors='replace')}")
+    return buf.raw[:nbytes]
+
+
+def bamsort_merge(ctx, runs):
+    """sg_bamsort_merge on an engine context (a c_void_p from sg_create, or Session.ctx): `runs` is a list of (records:
+    bytes, keys, lens), a run's records back to back.  Returns (record stream, BGZF members, keys, lens), the stream
+    sorted stably by key and the index in its order."""
+    eng = load_engine()
+    R = len(runs)
+    recs = (C.c_void_p * max(1, R))()
+    nbytes, counts = (C.c_uint64 * max(1, R))(), (C.c_uint64 * max(1, R))()
+    keyp, lenp = (C.POINTER(C.c_uint64) * max(1, R))(), (C.POINTER(C.c_uint32) * max(1, R))()
+    keep = []
+    for r, (records, keys, lens) in enumerate(runs):
+        rb = C.create_string_buffer(bytes(records), max(1, len(records)))
+        ka, la = (C.c_uint64 * max(1, len(keys)))(*keys), (C.c_uint32 * max(1, len(lens)))(*lens)
+        keep += [rb, ka, la]
+        recs[r] = C.cast(rb, C.c_void_p)
+        nbytes[r], counts[r] = len(records), len(keys)
+        keyp[r], lenp[r] = C.cast(ka, C.POINTER(C.c_uint64)), C.cast(la, C.POINTER(C.c_uint32))
+    ob, gb = C.c_uint64(), C.c_uint64()
+    rc = eng.sg_bamsort_merge(ctx, R, recs, nbytes, keyp, lenp, counts, C.byref(ob), C.byref(gb))
+    if rc != 0:
+        raise SimuError(f"sg_bamsort_merge (code {rc}): {eng.sg_last_error(ctx).decode(errors='replace')}")
+    keys, lens = _bamsort_index(eng, ctx)
+    return _bamsort_fetch(eng, ctx, False, ob.value), _bamsort_fetch(eng, ctx, True, gb.value), keys, lens
+
+
+def sort_tiles(runs, budget: int):
+    """simu_sort_tiles (host only, no GPU): how --truth-sort cuts the key space of sorted runs into tiles.  `runs`: a list
+    of (ascending keys, record lengths).  Returns [(first key, single)], ascending: tile i holds first_i <= key <
+    first_(i+1), the last all from its first on; single: one key value that alone exceeds the budget."""
+    lib = load_host()
+    R = len(runs)
+    keyp, prep = (C.POINTER(C.c_uint64) * max(1, R))(), (C.POINTER(C.c_uint64) * max(1, R))()
+    counts = (C.c_uint64 * max(1, R))()
+    keep = []
+    for r, (keys, lens) in enumerate(runs):
+        pre = [0]
+        for v in lens:
+            pre.append(pre[-1] + v)
+        ka, pa = (C.c_uint64 * max(1, len(keys)))(*keys), (C.c_uint64 * len(pre))(*pre)
+        keep += [ka, pa]
+        keyp[r], prep[r], counts[r] = C.cast(ka, C.POINTER(C.c_uint64)), C.cast(pa, C.POINTER(C.c_uint64)), len(keys)
+    n = lib.simu_sort_tiles(R, keyp, counts, prep, budget, None, None, 0)
+    if n == 2 ** 64 - 1:
+        raise SimuError("simu_sort_tiles refused the runs")
+    first, single = (C.c_uint64 * max(1, n))(), (C.c_uint8 * max(1, n))()
+    lib.simu_sort_tiles(R, keyp, counts, prep, budget, first, single, n)
+    return [(first[i], bool(single[i])) for i in range(n)]
+
+
 def errors_cells(cycles: int, n_qual: int, tmpl_len: int) -> int:
     """Cells of the true error counts' flat table (sg_errtab_counts): Q [2][cycles][n_qual][4] (bases, errors, other,
     inserted) | S [2][4][5] (from A C T G, to A C T G N) | I [2][L][2] | D [2][L][2] (events, bases)."""
@@ -721,6 +801,20 @@ class Session:
         a, b = C.c_uint64(), C.c_uint64()
         self._sg(self.eng.sg_truth_info(self.ctx, C.byref(a), C.byref(b)), "sg_truth_info")
         return a.value, b.value
+
+    # ---- the truth BAM in coordinate order (sg_bamsort_*) ----
+    def bamsort_pass(self, tags: int = 0):
+        """sg_bamsort_pass: truth_bam(tags) with the record stream in key order, uncompressed.  Returns (record bytes, records)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._sg(self.eng.sg_bamsort_pass(self.ctx, int(tags), C.byref(a), C.byref(b)), "sg_bamsort_pass")
+        return a.value, b.value
+
+    def bamsort_index(self):
+        """(keys, lengths) in output order of the last bamsort_pass() or bamsort_merge()."""
+        return _bamsort_index(self.eng, self.ctx)
+
+    def bamsort_fetch(self, compressed: bool, nbytes: int, offset: int = 0) -> bytes:
+        return _bamsort_fetch(self.eng, self.ctx, compressed, nbytes, offset)
 
     # ---- true coverage (sessions opened with truth_depth=BIN: the driver hands over the piece map and begins the depth
     # with the reference's contigs at the first prepare_batch; depth_begin starts one over contigs of the caller's) ----

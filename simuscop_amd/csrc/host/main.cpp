@@ -3,6 +3,7 @@
 //   --seed N  --device D  --out DIR  --no-write [--fetch]  --quiet  --rank R --world W  --stats  --host-haplotypes  --gzip
 //   --truth-bam   every read's true alignment as <stem>.truth.bam beside the FASTQ files (simulate.h)
 //   --truth-tags  with --truth-bam: NM, MD and XE tags on its records (XE: the read's true sequencing errors against its haplotype)
+//   --truth-sort  with --truth-bam: the file is coordinate-sorted (sorted on the device piece by piece, merged at the stem's close)
 //   --truth-depth BIN   the reads' true coverage as <stem>.truth.depth.bedgraph (BIN 1: runs of equal depth; BIN > 1: means)
 //   --truth-variants    per variant of the variation and SNP files the reads that cover the site and those that carry the
 //                       allele, as <stem>.truth.variants.tsv
@@ -234,6 +235,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--gzip") opt.gzip = 1;
     else if (a == "--truth-bam") opt.truth_bam = 1;
     else if (a == "--truth-tags") opt.truth_tags = 1;
+    else if (a == "--truth-sort") opt.truth_sort = 1;
     else if (a == "--truth-depth") {
       const char* v = val();
       char* end = nullptr;
@@ -303,7 +305,8 @@ int main(int argc, char* argv[]) {
             "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f truth_tag_bytes=%llu truth_md_dropped=%llu truth_nm_sum=%llu truth_xe_sum=%llu | "
             "variant_rows=%llu variant_dropped=%llu variant_hits=%llu variants_s=%.3f | "
             "depth_bases=%llu depth_rows=%llu depth_s=%.3f | "
-            "errors_bases=%llu errors_subst=%llu errors_s=%.3f\n",
+            "errors_bases=%llu errors_subst=%llu errors_s=%.3f | "
+            "truth_sort_runs=%llu truth_sort_tiles=%llu truth_spool_bytes=%llu truth_sort_s=%.3f\n",
             (unsigned long long)st.reads, (unsigned long long)st.fragments, (unsigned long long)st.fastq_bytes,
             (unsigned long long)st.windows, (unsigned long long)st.segments, (unsigned long long)st.batches, st.t_load,
             st.t_engine, st.t_reference,
@@ -315,6 +318,7 @@ int main(int argc, char* argv[]) {
             (unsigned long long)st.truth_tag_bytes, (unsigned long long)st.truth_md_dropped, (unsigned long long)st.truth_nm_sum, (unsigned long long)st.truth_xe_sum,
             (unsigned long long)st.variant_rows, (unsigned long long)st.variant_dropped, (unsigned long long)st.variant_hits, st.t_variants,
             (unsigned long long)st.depth_bases, (unsigned long long)st.depth_rows, st.t_depth,
-            (unsigned long long)st.errors_bases, (unsigned long long)st.errors_subst, st.t_errors);
+            (unsigned long long)st.errors_bases, (unsigned long long)st.errors_subst, st.t_errors,
+            (unsigned long long)st.truth_sort_runs, (unsigned long long)st.truth_sort_tiles, (unsigned long long)st.truth_spool_bytes, st.t_truth_sort);
   return 0;
 }

@@ -26,6 +26,7 @@
 #include "../../../include/simuscop_amd.h"
 #include "genome.h"
 #include "truth_outputs.h"
+#include "truth_sort.h"
 
 namespace simu {
 
@@ -120,7 +121,7 @@ struct Driver {
   std::unique_ptr<TruthOutputs> truth;
   // magic, header text, reference list (SAMv1 section 4.2) as BGZF members of their own, made by the device compressor
   void write_truth_header(FILE* f) {
-    std::string text = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
+    std::string text = opt.truth_sort ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
     for (size_t r = 0; r < contigs.name.size(); r++) text += "@SQ\tSN:" + contigs.name[r] + "\tLN:" + std::to_string(contigs.len[r]) + "\n";
     text += "@PG\tID:simuReads\n";
     std::string h("BAM\1", 4);
@@ -140,28 +141,37 @@ struct Driver {
     if (fwrite(gz.data(), 1, n, f) != n) throw Error("Error: short write to the truth BAM file", -1);
   }
   std::vector<uint8_t> truth_host;
+  // --truth-sort: the stem's spool and the index of its runs (truth_sort.h); made on first use
+  std::unique_ptr<TruthSort> tsort;
+  // the stem's sorted runs merged into its BAM, in front of the end-of-file block (nothing without a spool)
+  void close_truth_sort() {
+    if (tsort && tsort->active() && sink.ft) tsort->finish(sink.ft);
+  }
   // the records of the pass just sampled: made, compressed, counted and (unless --no-write) appended to the file.
   // Synchronous: the members are in the context's own buffer, which the next piece reuses.
   void truth_piece(Sink& sink) {
     auto t0 = Clock::now();
     uint64_t rb = 0, gb = 0, nrec = 0, nun = 0;
+    const uint32_t tags = opt.truth_tags ? SG_TAG_NM | SG_TAG_MD | SG_TAG_XE : 0u;
+    if (opt.truth_sort) eng.check(sg_bamsort_pass(eng.ctx, tags, &rb, nullptr), "sg_bamsort_pass");   // (uncompressed: gb stays 0 until the merge)
+    else if (opt.truth_tags) eng.check(sg_truth_bam_tags(eng.ctx, tags, &rb, &gb), "sg_truth_bam_tags");
+    else eng.check(sg_truth_bam(eng.ctx, &rb, &gb), "sg_truth_bam");
     if (opt.truth_tags) {
-      eng.check(sg_truth_bam_tags(eng.ctx, SG_TAG_NM | SG_TAG_MD | SG_TAG_XE, &rb, &gb), "sg_truth_bam_tags");
       sg_truth_tag_counts tc;
       eng.check(sg_truth_tag_info(eng.ctx, &tc), "sg_truth_tag_info");
       st.truth_tag_bytes += tc.tag_bytes;
       st.truth_md_dropped += tc.md_dropped;
       st.truth_nm_sum += tc.nm_sum;
       st.truth_xe_sum += tc.xe_sum;
-    } else {
-      eng.check(sg_truth_bam(eng.ctx, &rb, &gb), "sg_truth_bam");
     }
     eng.check(sg_truth_info(eng.ctx, &nrec, &nun), "sg_truth_info");
     st.truth_records += nrec;
     st.truth_unmapped += nun;
     st.truth_bytes += rb;
     st.truth_bgzf_bytes += gb;
-    if (opt.write_files && sink.ft && gb) {
+    if (opt.truth_sort) {
+      if (opt.write_files && sink.ft && rb && tsort && tsort->active()) tsort->add_run(rb);
+    } else if (opt.write_files && sink.ft && gb) {
       if (truth_host.size() < gb) truth_host.resize(gb);
       eng.check(sg_fetch_truth(eng.ctx, 1, 0, gb, truth_host.data()), "sg_fetch_truth");
       if (fwrite(truth_host.data(), 1, gb, sink.ft) != gb) throw Error("Error: short write to the truth BAM file", -1);
@@ -173,6 +183,10 @@ struct Driver {
     if (!opt.truth_bam) return;
     sink.open_truth(dir, stem, suffix);
     if (opt.shard_world <= 1 || opt.shard_rank == 0) write_truth_header(sink.ft);
+    if (opt.truth_sort) {
+      if (!tsort) tsort.reset(new TruthSort(eng, st));
+      tsort->open(dir + "/" + stem + ".truth.bam" + suffix);
+    }
   }
 
   void upload(const std::string& popu, const std::string& chr) {
@@ -819,6 +833,7 @@ struct Driver {
           stem += buf;
         }
         drain_wait();  // the previous mixture's last batch still writes into the files about to be closed
+        close_truth_sort();
         truth->close();
         if (opt.write_files) open_sink(out_dir, stem, paired, suffix);
         truth->open(out_dir, stem);
@@ -830,6 +845,7 @@ struct Driver {
       }
     }
     drain_wait();
+    close_truth_sort();
     truth->close();
     sink.close();
     log("\nReads generation done!\n");

@@ -45,6 +45,11 @@ typedef struct simu_options {
                            //    FASTQ parts: rank 0's carries the header, the last rank's the BGZF end-of-file block
   int32_t truth_tags;      // 1: with truth_bam, its records carry NM, MD and XE tags (sg_truth_bam_tags; the rule: DESIGN.md "Truth
                            //    tags"); refused without truth_bam
+  int32_t truth_sort;      // 1: with truth_bam, <stem>.truth.bam is coordinate-sorted (@HD SO:coordinate; the order: DESIGN.md "Sorted
+                           //    truth BAM"): every piece is sorted on the device (sg_bamsort_pass) and spooled to
+                           //    <stem>.truth.bam.runs.tmp, the runs are merged on the device at the stem's close (sg_bamsort_merge),
+                           //    SIMU_SORT_TILE_BYTES of records at a time.  Refused without truth_bam and in a sharded run (sorted
+                           //    parts cannot be concatenated)
   int32_t truth_errors;    // 1: write per mate, cycle and reported quality how many bases were really wrong -- the read against the
                            //    haplotype bases it was cut from, so a variant allele is no error -- with a substitution matrix and
                            //    the sequencing indels to <stem>.truth.errors.tsv beside the FASTQ files (sg_errtab_*; the rule:
@@ -95,6 +100,10 @@ typedef struct simu_stats {
   uint64_t truth_md_dropped;  // ... mapped records left without MD (a text longer than the engine's cap), ...
   uint64_t truth_nm_sum;      // ... and the sums of the NM and of the XE values
   uint64_t truth_xe_sum;
+  uint64_t truth_sort_runs;   // truth_sort: sorted runs spooled (one per piece with records), ...
+  uint64_t truth_sort_tiles;  // ... tiles of the key space they were merged in, ...
+  uint64_t truth_spool_bytes; // ... bytes the spool files held
+  double t_truth_sort;        // ... and the merges at the stems' close: cutting, reading the spool, sg_bamsort_merge, writing
   uint64_t errors_bases;   // truth_errors: read bases paired with an A/C/G/T template base, ...
   uint64_t errors_subst;   // ... of which the read shows another letter
   double t_errors;         // sg_errtab_* calls, formatting and writing the table
@@ -150,6 +159,18 @@ uint64_t simu_variants_format(const char* const* contig_name, const uint64_t* co
                               const char* const* text, uint64_t n_in, const uint32_t* counts, uint64_t n_counts, void* table,
                               uint64_t table_cap, char* out, uint64_t cap, uint64_t* rows, uint64_t* dropped);
 
+// How --truth-sort cuts the key space of a stem's sorted runs into tiles that fit the device, host only.  Run r holds
+// n[r] records with ascending keys[r][i]; prefix[r] holds n[r] + 1 prefix sums of their bytes (prefix[r][0] = 0).  The
+// result is `tiles` ascending splitter keys K_i: tile i holds the records with K_i <= key < K_(i+1), the last tile all
+// from its K on; every tile holds a record, and together they hold every record once.  A tile takes as many bytes as fit
+// under `budget`, except a tile that consists of one key value: that one may exceed it and is then marked in single[i]
+// (all its keys are equal, so it needs no sort: the merged order is the runs in order).  The rule: bytes(key < K) = the
+// sum over r of prefix[r][lower_bound(keys[r], K)] is monotone in K, so a binary search over K finds each splitter.
+// Returns the number of tiles and writes the first min(tiles, cap) splitters and marks (either array may be NULL);
+// UINT64_MAX: a NULL table.
+uint64_t simu_sort_tiles(uint32_t n_runs, const uint64_t* const* keys, const uint64_t* n, const uint64_t* const* prefix, uint64_t budget,
+                         uint64_t* splitters, uint8_t* single, uint64_t cap);
+
 // ---- step-by-step session (bench.py / multi-GPU launcher) ----
 typedef struct simu_session simu_session;
 int simu_open(const char* config_path, const simu_options* opt, simu_session** out, char* err, size_t err_len);
@@ -179,6 +200,10 @@ inline std::string simu_truth_refusal(const simu_options& o, bool sharded, bool 
   const Rule rules[] = {{"--truth-bam", o.truth_bam, false, true, nullptr}, {"--truth-depth", o.truth_depth, true, true, "depths"},
                         {"--truth-variants", o.truth_variants, false, true, "counts"}, {"--truth-errors", o.truth_errors, false, false, "tables"}};
   if (o.truth_tags && !o.truth_bam) return "Error: --truth-tags needs --truth-bam: the tags go on the truth BAM's records";
+  if (o.truth_sort && !o.truth_bam) return "Error: --truth-sort needs --truth-bam: it is the truth BAM's records that are sorted";
+  if (o.truth_sort && sharded)
+    return "Error: --truth-sort cannot be combined with --world or --gpus above 1: the ranks' sorted parts would have to be merged, not "
+           "concatenated";
   for (const Rule& r : rules) {
     if (all && r.is_width && r.on < 0) return std::string("Error: ") + r.flag + " needs a bin width of at least 1";
     if (all && r.on && r.needs_map && o.host_haplotypes)

@@ -818,9 +818,8 @@ uint32_t sg_deflate_plan(const uint64_t lit_counts[286], const uint64_t dist_cou
   return plan.prefix_bits;
 }
 
-// `bytes` (> 0) of text on the device -> its BGZF members in `gz`, *gz_total bytes of them.  `text` is followed by 64
-// readable bytes, as the sampler's output buffers are.  What sg_compress does per mate and sg_deflate_bgzf for its caller.
-static int deflate_text(sg_ctx* ctx, const uint8_t* text, uint64_t bytes, DevBuf& gz, uint64_t* gz_total, const char* who) {
+// (declared in sg_api.h, not part of the ABI)
+extern "C++" int deflate_text(sg_ctx* ctx, const uint8_t* text, uint64_t bytes, DevBuf& gz, uint64_t* gz_total, const char* who) {
   hipStream_t s = ctx->stream;
   if (bytes / sg::kGzChunk >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": text too large");
   const uint32_t n_chunks = (uint32_t)((bytes + sg::kGzChunk - 1) / sg::kGzChunk);
@@ -1108,10 +1107,14 @@ static_assert(SG_TAG_NM == sg::kTagNM && SG_TAG_MD == sg::kTagMD && SG_TAG_XE ==
 
 int sg_truth_bam(sg_ctx* ctx, uint64_t* record_bytes, uint64_t* bgzf_bytes) { return sg_truth_bam_tags(ctx, 0, record_bytes, bgzf_bytes); }
 
-// With tags == 0 exactly the kernels of the untagged stream are launched and nothing of the tags is allocated.
 int sg_truth_bam_tags(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
+  return sg_pass_records(ctx, tags ? "sg_truth_bam_tags" : "sg_truth_bam", tags, false, record_bytes, bgzf_bytes);
+}
+
+// With tags == 0 exactly the kernels of the untagged stream are launched and nothing of the tags is allocated; with
+// sorted == false nothing of the sort is launched or allocated.  (Declared in sg_api.h, not part of the ABI.)
+extern "C++" int sg_pass_records(sg_ctx* ctx, const char* who, uint32_t tags, bool sorted, uint64_t* record_bytes, uint64_t* bgzf_bytes) {
   if (!ctx) return SG_ERR_INVALID;
-  const char* const who = tags ? "sg_truth_bam_tags" : "sg_truth_bam";
   if (tags & ~(uint32_t)(SG_TAG_NM | SG_TAG_MD | SG_TAG_XE)) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: tags is a mask of SG_TAG_NM, SG_TAG_MD and SG_TAG_XE");
   sg::TruthJob J;
   memset(&J, 0, sizeof J);
@@ -1125,7 +1128,7 @@ int sg_truth_bam_tags(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64
   sg_ctx::Pass& Q = ctx->pass;
   const sg::DevBatch& B = ctx->B;
   const uint32_t N = J.map.n_reads;
-  Q.have_bam = false;
+  Q.have_bam = Q.bam_sorted = false;
   Q.bam_rec_bytes = Q.bam_gz_bytes = Q.bam_records = Q.bam_unmapped = 0;
   for (uint64_t& v : Q.bam_tags) v = 0;
   hipStream_t s = ctx->stream;
@@ -1160,13 +1163,16 @@ int sg_truth_bam_tags(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64
     SG_HIP(hipMemsetAsync(G.counters, 0, 64, s));
   }
   uint64_t c[8] = {};
+  int sort_rc = SG_OK;
   if (int rc = sg_run_counted(ctx, wk, 8, c, [&]() {
         if (!N) return;
         sg::launch_truth_size(ctx->P, B, J, s);
         if (tags) sg::launch_truth_tag_size(ctx->P, B, J, G, s);
-        sg::launch_scan_u32(J.rec_len, N, (uint64_t*)(wk + off_bsum), (uint64_t*)(wk + off_off), (uint64_t*)(wk + 32), s);
+        if (!sorted) sg::launch_scan_u32(J.rec_len, N, (uint64_t*)(wk + off_bsum), (uint64_t*)(wk + off_off), (uint64_t*)(wk + 32), s);
+        else sort_rc = bamsort_pass_keys(ctx, J, B.paired != 0);
       }))
     return rc;
+  if (sort_rc) return sort_rc;
   if (c[2] & 3) return ctx->fail(SG_ERR_OVERFLOW, std::string(who) + ": an alignment with more than " + std::to_string(sg::kTruthMaxOps) + " operations");
   uint64_t tc[8] = {};
   if (tags) {
@@ -1174,6 +1180,9 @@ int sg_truth_bam_tags(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64
     if (tc[7] & 1) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: a read whose events or operations do not end at its length");
     if (tc[7] & 2) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: an alignment outside its contig of the committed reference");
     if (tc[7] & 4) return ctx->fail(SG_ERR_INVALID, "sg_truth_bam_tags: a record outside its mate's text");
+  }
+  if (sorted) {   // rec_off by read index from the lengths in key order
+    if (int rc = bamsort_pass_order(ctx, J, (uint64_t*)(wk + off_off), &c[4])) return rc;
   }
   const uint64_t total = c[4];
   if (total) {
@@ -1185,13 +1194,15 @@ int sg_truth_bam_tags(sg_ctx* ctx, uint32_t tags, uint64_t* record_bytes, uint64
     uint64_t flags = 0;
     if (int rc = sg_read_back(ctx, &flags, wk + 16, 8)) return rc;
     if (flags & 4) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": a record does not fit the record kernel's stages");
-    if (int rc = deflate_text(ctx, T.rec.as<uint8_t>(), total, T.gz, &Q.bam_gz_bytes, who)) return rc;
+    if (!sorted)
+      if (int rc = deflate_text(ctx, T.rec.as<uint8_t>(), total, T.gz, &Q.bam_gz_bytes, who)) return rc;
   }
   for (int i = 0; i < 7; i++) Q.bam_tags[i] = tc[i];
   Q.bam_rec_bytes = total;
   Q.bam_records = c[0];
   Q.bam_unmapped = c[1];
   Q.have_bam = true;
+  Q.bam_sorted = sorted;
   if (record_bytes) *record_bytes = Q.bam_rec_bytes;
   if (bgzf_bytes) *bgzf_bytes = Q.bam_gz_bytes;
   return SG_OK;

@@ -1,7 +1,7 @@
 // sg_api.h -- what the files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
 // sink, reference, haplotypes), sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM
 // input), sg_api_depth.cpp (true coverage), sg_api_variants.cpp (true allele counts) and sg_api_errors.cpp (true error
-// counts).  Internal: the ABI itself is include/simuscop_amd.h.
+// counts) and sg_api_bamsort.cpp (the truth BAM in coordinate order).  Internal: the ABI itself is include/simuscop_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -104,6 +104,17 @@ struct sg_ctx {
     uint64_t bases = 0, errors = 0, skipped = 0, reads = 0;
     DevBuf table;
   } errtab;
+  // the truth BAM in coordinate order (sg_bamsort_*, sg_api_bamsort.cpp): the keys and payloads of the sort (two of each:
+  // a digit pass goes from one to the other; `cur` holds the result), the records' lengths in output order, `work` the
+  // counters, histograms and offsets of a call; of a merge also its input records, output stream and members.  `n`
+  // records are indexed while `have` (a merge) or the pass says bam_sorted.  Without a sg_bamsort_* call nothing is
+  // kept and nothing is allocated.
+  struct BamSort {
+    bool have = false;
+    int cur = 0;
+    uint64_t n = 0, out_bytes = 0, gz_bytes = 0;
+    DevBuf keys[2], vals[2], lens, work, src, out, gz;
+  } bamsort;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // the window planner (sg_gc_percent, sg_window_weights, sg_windows_*, sg_plan_windows / sg_plan_range;
   // sg_api_windows.cpp): `stores` holds the window weights of sg_windows_build per store id, `plan` the batch table of
@@ -159,6 +170,7 @@ struct sg_ctx {
     bool have_gz = false;             // sg_compress: gz1 / gz2 hold gz_bytes of members
     uint64_t gz_bytes[2] = {0, 0};
     bool have_bam = false;            // sg_truth_bam: truth.rec / truth.gz hold the pass's records
+    bool bam_sorted = false;          // ... made by sg_bamsort_pass: in key order, uncompressed, indexed by ctx->bamsort
     uint64_t bam_rec_bytes = 0, bam_gz_bytes = 0, bam_records = 0, bam_unmapped = 0;
     uint64_t bam_tags[7] = {0, 0, 0, 0, 0, 0, 0};   // sg_truth_bam_tags: records with NM, MD, XE, the sums of NM and XE, MD texts dropped, tag bytes
   } pass;
@@ -203,6 +215,19 @@ int sg_pass_need(sg_ctx* ctx, const char* who, sg_ctx::Pass::Stage at_least, boo
 // of sg_plan and sg_plan_range.  Internal like the two above, not part of the ABI.  Defined in sg_api.cpp.
 int finish_plan(sg_ctx* ctx, uint64_t nw, uint32_t n_segs, uint32_t n_slots, uint32_t batch_id, uint32_t first_window,
                 uint32_t first_slot, int32_t paired, const char* name_prefix);
+// `bytes` (> 0) of text on the device -> its BGZF members in `gz`, *gz_total bytes of them.  `text` is followed by 64
+// readable bytes, as the sampler's output buffers are.  What sg_compress does per mate, sg_deflate_bgzf for its caller,
+// sg_truth_bam for its records and sg_bamsort_merge for its stream.  Defined in sg_api.cpp.
+int deflate_text(sg_ctx* ctx, const uint8_t* text, uint64_t bytes, DevBuf& gz, uint64_t* gz_total, const char* who);
+// The records of the pass just sampled into truth.rec (sg_truth_bam_tags; `sorted`: sg_bamsort_pass, whose stream is in
+// key order and stays uncompressed).  Defined in sg_api.cpp.
+int sg_pass_records(sg_ctx* ctx, const char* who, uint32_t tags, bool sorted, uint64_t* record_bytes, uint64_t* bgzf_bytes);
+// The two steps sg_pass_records takes for a sorted pass (sg_api_bamsort.cpp).  bamsort_pass_keys, behind the sizing
+// kernels on the stream: the live records' keys.  bamsort_pass_order, once the stream has been waited for: sorts them and
+// fills `rec_off` by read index with the scan of the lengths in key order; *total = bytes of the stream.
+namespace sg { struct TruthJob; }
+int bamsort_pass_keys(sg_ctx* ctx, const sg::TruthJob& J, bool paired);
+int bamsort_pass_order(sg_ctx* ctx, const sg::TruthJob& J, uint64_t* rec_off, uint64_t* total);
 // no context, or a call in front of its output's X_begin
 inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
   if (!ctx) return SG_ERR_INVALID;
