@@ -456,6 +456,43 @@ int sg_bamsort_merge(sg_ctx* ctx, uint32_t n_runs, const void* const* records, c
 int sg_bamsort_index(sg_ctx* ctx, uint64_t* keys_out, uint32_t* lens_out, uint64_t cap, uint64_t* n);
 int sg_bamsort_fetch(sg_ctx* ctx, int compressed, uint64_t offset, uint64_t bytes, void* host_dst);
 
+/* ---- the BAI index of the sorted truth BAM (simuReads --truth-index) --------------------------------
+ * The index is stated once, in csrc/sg_bamindex.h.  A call indexes the records of one compressed text while the text and
+ * the member offsets of its compression are still on the device; the host joins the calls' chunk rows and serialises
+ * (simu_bai_build, host/simulate.h).  Opt-in: a context that never calls these launches no kernel of this part and
+ * holds no memory for it.
+ *   sg_bamindex_begin   a stem starts: n_ref references of ref_len[] bases; the linear index (the sum of ceil(len / 16384)
+ *                       cells, all ~0) and the counts are reset.  A length above 2^29: SG_ERR_UNSUPPORTED, and the
+ *                       index of an earlier sg_bamindex_begin stays as it was
+ *   sg_bamindex_add     indexes the records of the context's latest compression, whose first member lies at file_offset
+ *                       of the BAM file.  source SG_BAMINDEX_MERGE: the output of the last sg_bamsort_merge, whose
+ *                       lengths and offsets are on the device (lens NULL, skip 0).  SG_BAMINDEX_DEFLATE: the text of the
+ *                       last sg_deflate_bgzf; lens[n] are the lengths of the records that start in it, the first at
+ *                       `skip` (the bytes in front belong to a record begun in an earlier text).  Only the last may run
+ *                       past the text: it is kept on the device and indexed as the first record of the next call, which
+ *                       must be a SG_BAMINDEX_DEFLATE one whose skip is the record's rest.  *n_chunks = chunk rows of
+ *                       the call, *first_voff = the start offset of its first record (~0: it indexed none).  A source
+ *                       that is not the latest compression, a record that does not parse or lies outside its reference:
+ *                       SG_ERR_INVALID; after a failure of the kernels the stem's index is void (sg_bamindex_begin again)
+ *   sg_bamindex_chunks  the chunk rows of the last sg_bamindex_add, grouped by key = refID << 32 | bin, keys ascending,
+ *                       file order within a key; the chunk that ends the call has end = ~0 (the caller closes it with the
+ *                       next call's first_voff, or with the end-of-file block's offset << 16).  rows NULL: only *n
+ *   sg_bamindex_finish  the stem's linear index (`cap` cells of room; untouched windows are ~0, simu_bai_build fills
+ *                       them) and counts[3 n_ref + 1]: per reference records without 0x4, records with 0x4, the
+ *                       smallest start offset (~0: no record); then the records with refID -1
+ *   sg_bamindex_end     gives the part's memory back                                                                  */
+#define SG_BAMINDEX_MERGE 0
+#define SG_BAMINDEX_DEFLATE 1
+typedef struct sg_bai_chunk {
+  uint64_t key, beg, end;
+} sg_bai_chunk;
+int sg_bamindex_begin(sg_ctx* ctx, uint32_t n_ref, const uint64_t* ref_len);
+int sg_bamindex_add(sg_ctx* ctx, int source, uint64_t file_offset, uint64_t skip, const uint32_t* lens, uint64_t n, uint64_t* n_chunks,
+                    uint64_t* first_voff);
+int sg_bamindex_chunks(sg_ctx* ctx, sg_bai_chunk* rows, uint64_t cap, uint64_t* n);
+int sg_bamindex_finish(sg_ctx* ctx, uint64_t* linear, uint64_t cap, uint64_t* counts);
+int sg_bamindex_end(sg_ctx* ctx);
+
 /* ---- true coverage: the depth the reads of all passes really laid down (simuReads --truth-depth) -------------------
  * Coverage adds up, so it needs no sort: one int32 difference array over the reference (len + 1 slots per contig, 4
  * bytes per reference base) takes +1 / -1 for every M run of every read's true alignment (the rule above), pass after

@@ -34,6 +34,7 @@ ENGINE_SYMBOLS = [
     "sg_truth_align", "sg_truth_map", "sg_truth_pieces", "sg_truth_reads", "sg_truth_bam", "sg_fetch_truth", "sg_truth_info",
     "sg_truth_bam_tags", "sg_truth_tag_info", "sg_truth_tags",
     "sg_bamsort_pass", "sg_bamsort_merge", "sg_bamsort_index", "sg_bamsort_fetch",
+    "sg_bamindex_begin", "sg_bamindex_add", "sg_bamindex_chunks", "sg_bamindex_finish", "sg_bamindex_end",
     "sg_depth_begin", "sg_depth_add", "sg_depth_add_spans", "sg_depth_bins", "sg_depth_runs", "sg_depth_fetch", "sg_depth_reset",
     "sg_depth_info", "sg_depth_end",
     "sg_variants_begin", "sg_variants_add", "sg_variants_counts", "sg_variants_reset", "sg_variants_info", "sg_variants_end",
@@ -162,7 +163,7 @@ class SimuOptions(C.Structure):
                 ("fetch", C.c_int32), ("quiet", C.c_int32), ("shard_rank", C.c_int32), ("shard_world", C.c_int32),
                 ("output_dir", C.c_char_p), ("repeat_sample", C.c_int32), ("host_haplotypes", C.c_int32), ("gzip", C.c_int32),
                 ("shard_contigs", C.c_int32), ("no_eof_block", C.c_int32), ("exchange", C.c_void_p), ("exchange_user", C.c_void_p),
-                ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_bam", C.c_int32),
+                ("crlf_as_lf", C.c_int32), ("strict_bases", C.c_int32), ("unique_contigs", C.c_int32), ("truth_index", C.c_int32), ("truth_bam", C.c_int32),
                 ("truth_tags", C.c_int32), ("truth_sort", C.c_int32), ("truth_errors", C.c_int32), ("truth_variants", C.c_int32), ("truth_depth", C.c_int32)]
 
 
@@ -185,6 +186,7 @@ class SimuStats(C.Structure):
                 ("t_reference", C.c_double), ("t_hap_device", C.c_double), ("t_plan_api", C.c_double), ("t_compress", C.c_double), ("gz_bytes", C.c_uint64),
                 ("emit_kernel", C.c_int32), ("emit_slow_rows_lds", C.c_int32), ("emit_lds_bytes", C.c_uint32),
                 ("emit_clean_cap", C.c_uint32),
+                ("bai_bins", C.c_uint64), ("bai_chunks", C.c_uint64), ("bai_bytes", C.c_uint64), ("t_bai", C.c_double),
                 ("truth_records", C.c_uint64), ("truth_unmapped", C.c_uint64), ("truth_bytes", C.c_uint64),
                 ("truth_bgzf_bytes", C.c_uint64), ("t_truth", C.c_double),
                 ("truth_tag_bytes", C.c_uint64), ("truth_md_dropped", C.c_uint64), ("truth_nm_sum", C.c_uint64), ("truth_xe_sum", C.c_uint64),
@@ -302,6 +304,11 @@ def load_engine():
     lib.sg_bamsort_merge.argtypes = [vp, C.c_uint32, C.POINTER(vp), u64p, C.POINTER(u64p), C.POINTER(u32p), u64p, u64p, u64p]
     lib.sg_bamsort_index.argtypes = [vp, u64p, u32p, C.c_uint64, u64p]
     lib.sg_bamsort_fetch.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
+    lib.sg_bamindex_begin.argtypes = [vp, C.c_uint32, u64p]
+    lib.sg_bamindex_add.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u64p]
+    lib.sg_bamindex_chunks.argtypes = [vp, C.c_void_p, C.c_uint64, u64p]
+    lib.sg_bamindex_finish.argtypes = [vp, u64p, C.c_uint64, u64p]
+    lib.sg_bamindex_end.argtypes = [vp]
     lib.sg_depth_begin.argtypes = [vp, u64p, C.c_uint32]
     lib.sg_depth_add.argtypes = [vp, u64p]
     lib.sg_depth_add_spans.argtypes = [vp, u32p, u64p, u64p, C.c_uint64]
@@ -375,6 +382,8 @@ def load_host():
     lib.simu_errors_format.restype = C.c_uint64
     lib.simu_sort_tiles.argtypes = [C.c_uint32, C.POINTER(u64p), u64p, C.POINTER(u64p), C.c_uint64, u64p, C.POINTER(C.c_uint8), C.c_uint64]
     lib.simu_sort_tiles.restype = C.c_uint64
+    lib.simu_bai_build.argtypes = [C.c_uint32, u64p, C.c_void_p, C.c_uint64, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
+    lib.simu_bai_build.restype = C.c_uint64
     _host = lib
     return lib
 
@@ -619,6 +628,77 @@ def bamsort_merge(ctx, runs):
         raise SimuError(f"sg_bamsort_merge (code {rc}): {eng.sg_last_error(ctx).decode(errors='replace')}")
     keys, lens = _bamsort_index(eng, ctx)
     return _bamsort_fetch(eng, ctx, False, ob.value), _bamsort_fetch(eng, ctx, True, gb.value), keys, lens
+
+
+BAMINDEX_MERGE, BAMINDEX_DEFLATE = 0, 1   # SG_BAMINDEX_*: whose records sg_bamindex_add indexes
+BAI_OPEN = 2 ** 64 - 1                    # the end of the chunk that ends a call, until the caller closes it
+
+
+def _bamindex_check(eng, ctx, rc, who):
+    if rc != 0:
+        raise SimuError(f"{who} (code {rc}): {eng.sg_last_error(ctx).decode(errors='replace')}")
+
+
+def bamindex_begin(ctx, ref_len) -> None:
+    """sg_bamindex_begin on an engine context: a stem of len(ref_len) references starts."""
+    eng = load_engine()
+    _bamindex_check(eng, ctx, eng.sg_bamindex_begin(ctx, len(ref_len), (C.c_uint64 * max(1, len(ref_len)))(*ref_len)), "sg_bamindex_begin")
+
+
+def bamindex_add(ctx, source: int, file_offset: int, skip: int = 0, lens=None):
+    """sg_bamindex_add: index the records of the context's latest compression (BAMINDEX_MERGE: of bamsort_merge;
+    BAMINDEX_DEFLATE: of sg_deflate_bgzf, with the lengths of the records that start in its text).  Returns (chunk rows
+    [(key, beg, end)] grouped by key = refID << 32 | bin, first_voff)."""
+    eng = load_engine()
+    nc, fv = C.c_uint64(), C.c_uint64()
+    n = 0 if lens is None else len(lens)
+    la = None if lens is None else (C.c_uint32 * max(1, n))(*lens)
+    _bamindex_check(eng, ctx, eng.sg_bamindex_add(ctx, source, file_offset, skip, la, n, C.byref(nc), C.byref(fv)), "sg_bamindex_add")
+    return bamindex_chunks(ctx), fv.value
+
+
+def bamindex_chunks(ctx):
+    """sg_bamindex_chunks: the chunk rows of the last bamindex_add as [(key, beg, end)]."""
+    eng = load_engine()
+    n = C.c_uint64()
+    _bamindex_check(eng, ctx, eng.sg_bamindex_chunks(ctx, None, 0, C.byref(n)), "sg_bamindex_chunks")
+    rows = (C.c_uint64 * max(1, 3 * n.value))()
+    _bamindex_check(eng, ctx, eng.sg_bamindex_chunks(ctx, rows, n.value, C.byref(n)), "sg_bamindex_chunks")
+    return [(rows[3 * i], rows[3 * i + 1], rows[3 * i + 2]) for i in range(n.value)]
+
+
+def bamindex_finish(ctx, ref_len):
+    """sg_bamindex_finish: (linear index cells of all references back to back, counts[3 n_ref + 1])."""
+    eng = load_engine()
+    n_win = sum((ln + 16383) >> 14 for ln in ref_len)
+    lin, cnt = (C.c_uint64 * max(1, n_win))(), (C.c_uint64 * (3 * len(ref_len) + 1))()
+    _bamindex_check(eng, ctx, eng.sg_bamindex_finish(ctx, lin, n_win, cnt), "sg_bamindex_finish")
+    return list(lin[:n_win]), list(cnt)
+
+
+def deflate_bgzf(ctx, text: bytes) -> bytes:
+    """sg_deflate_bgzf on an engine context: the BGZF members of `text` (no end-of-file block)."""
+    eng = load_engine()
+    cap = len(text) + len(text) // 2 + 1024 * (len(text) // 32768 + 2)
+    out, n = C.create_string_buffer(cap), C.c_uint64()
+    _bamindex_check(eng, ctx, eng.sg_deflate_bgzf(ctx, text, len(text), out, cap, C.byref(n)), "sg_deflate_bgzf")
+    return out.raw[:n.value]
+
+
+def bai_build(ref_len, rows, linear, counts):
+    """simu_bai_build (host only, no GPU): the bytes of a BAI from chunk rows [(key, beg, end)] of all calls in call order
+    with every open end closed, the linear cells and the counts.  Returns (bytes, bins, chunks)."""
+    lib = load_host()
+    R = len(ref_len)
+    flat = (C.c_uint64 * max(1, 3 * len(rows)))(*[v for row in rows for v in row])
+    la, ca, ra = (C.c_uint64 * max(1, len(linear)))(*linear), (C.c_uint64 * len(counts))(*counts), (C.c_uint64 * max(1, R))(*ref_len)
+    bins, chunks = C.c_uint64(), C.c_uint64()
+    n = lib.simu_bai_build(R, ra, flat, len(rows), la, ca, None, 0, C.byref(bins), C.byref(chunks))
+    if n == 2 ** 64 - 1:
+        raise SimuError("simu_bai_build refused the tables")
+    out = C.create_string_buffer(max(1, n))
+    lib.simu_bai_build(R, ra, flat, len(rows), la, ca, out, n, C.byref(bins), C.byref(chunks))
+    return out.raw[:n], bins.value, chunks.value
 
 
 def sort_tiles(runs, budget: int):

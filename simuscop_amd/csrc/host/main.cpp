@@ -4,6 +4,7 @@
 //   --truth-bam   every read's true alignment as <stem>.truth.bam beside the FASTQ files (simulate.h)
 //   --truth-tags  with --truth-bam: NM, MD and XE tags on its records (XE: the read's true sequencing errors against its haplotype)
 //   --truth-sort  with --truth-bam: the file is coordinate-sorted (sorted on the device piece by piece, merged at the stem's close)
+//   --truth-index with --truth-bam --truth-sort: <stem>.truth.bam.bai beside the sorted file, its rows made on the device
 //   --truth-depth BIN   the reads' true coverage as <stem>.truth.depth.bedgraph (BIN 1: runs of equal depth; BIN > 1: means)
 //   --truth-variants    per variant of the variation and SNP files the reads that cover the site and those that carry the
 //                       allele, as <stem>.truth.variants.tsv
@@ -236,6 +237,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--truth-bam") opt.truth_bam = 1;
     else if (a == "--truth-tags") opt.truth_tags = 1;
     else if (a == "--truth-sort") opt.truth_sort = 1;
+    else if (a == "--truth-index") opt.truth_index = 1;
     else if (a == "--truth-depth") {
       const char* v = val();
       char* end = nullptr;
@@ -302,6 +304,7 @@ int main(int argc, char* argv[]) {
     fprintf(stderr,
             "stats: reads=%llu fragments=%llu bytes=%llu windows=%llu segments=%llu batches=%llu | load %.3fs (engine %.3fs reference %.3fs) haplotypes %.3fs "
             "plan %.3fs sample %.3fs (haplotype calls %.3fs sg_plan %.3fs) fetch %.3fs write %.3fs total %.3fs | kernels ms: plan %.3f namebase %.3f indel %.3f scan %.3f emit %.3f emit_slow %.3f | queued_items=%llu requeued_batches=%llu emit_kernel=%d slow_rows_lds=%d emit_lds=%u clean_cap=%u | compress %.3fs gz_bytes=%llu | "
+            "bai_bins=%llu bai_chunks=%llu bai_bytes=%llu bai_s=%.3f | "
             "truth_records=%llu truth_unmapped=%llu truth_bytes=%llu truth_bgzf_bytes=%llu truth_s=%.3f truth_tag_bytes=%llu truth_md_dropped=%llu truth_nm_sum=%llu truth_xe_sum=%llu | "
             "variant_rows=%llu variant_dropped=%llu variant_hits=%llu variants_s=%.3f | "
             "depth_bases=%llu depth_rows=%llu depth_s=%.3f | "
@@ -313,7 +316,8 @@ int main(int argc, char* argv[]) {
             st.t_haplotypes, st.t_plan, st.t_sample, st.t_hap_device, st.t_plan_api, st.t_fetch, st.t_write, st.t_total, st.kernel_ms[0], st.kernel_ms[1],
             st.kernel_ms[2], st.kernel_ms[3], st.kernel_ms[4], st.kernel_ms[5], (unsigned long long)st.queued_items,
             (unsigned long long)st.requeued_batches, st.emit_kernel, st.emit_slow_rows_lds, st.emit_lds_bytes,
-            st.emit_clean_cap, st.t_compress, (unsigned long long)st.gz_bytes, (unsigned long long)st.truth_records,
+            st.emit_clean_cap, st.t_compress, (unsigned long long)st.gz_bytes,
+            (unsigned long long)st.bai_bins, (unsigned long long)st.bai_chunks, (unsigned long long)st.bai_bytes, st.t_bai, (unsigned long long)st.truth_records,
             (unsigned long long)st.truth_unmapped, (unsigned long long)st.truth_bytes, (unsigned long long)st.truth_bgzf_bytes, st.t_truth,
             (unsigned long long)st.truth_tag_bytes, (unsigned long long)st.truth_md_dropped, (unsigned long long)st.truth_nm_sum, (unsigned long long)st.truth_xe_sum,
             (unsigned long long)st.variant_rows, (unsigned long long)st.variant_dropped, (unsigned long long)st.variant_hits, st.t_variants,

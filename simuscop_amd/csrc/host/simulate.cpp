@@ -184,7 +184,10 @@ struct Driver {
     sink.open_truth(dir, stem, suffix);
     if (opt.shard_world <= 1 || opt.shard_rank == 0) write_truth_header(sink.ft);
     if (opt.truth_sort) {
-      if (!tsort) tsort.reset(new TruthSort(eng, st));
+      if (!tsort) {
+        tsort.reset(new TruthSort(eng, st));
+        if (opt.truth_index) tsort->index_with(contigs.len);
+      }
       tsort->open(dir + "/" + stem + ".truth.bam" + suffix);
     }
   }
@@ -783,6 +786,10 @@ struct Driver {
     genome.load_data();
     st.t_reference = genome.t_reference;
     contigs.build(genome.fa);
+    if (opt.truth_index)   // (before any file of a stem is opened)
+      for (size_t r = 0; r < contigs.len.size(); r++)
+        if (contigs.len[r] > (1ull << 29))
+          throw Error("Error: --truth-index cannot index contig " + contigs.name[r] + ": it is longer than 2^29 bases, which a BAI cannot address", 1);
     truth.reset(new TruthOutputs(eng, opt, st, contigs, genome, cfg, prof));
     const std::string out_dir = (opt.output_dir && opt.output_dir[0]) ? opt.output_dir : cfg.str["output"];
     if (opt.write_files) {  // `mkdir -p` (src/simuReads.cpp:56-60)

@@ -39,6 +39,10 @@ typedef struct simu_options {
                            //    holder of the short contexts, Profile.cpp:94-101, 220-226)
   int32_t unique_contigs;  // 1: refuse a FASTA that holds a contig name twice (default: the name stands twice in the
                            //    chromosome list and both resolve to the first sequence, Fasta.cpp:67,84-97,198)
+  int32_t truth_index;     // 1: with truth_bam and truth_sort, <stem>.truth.bam.bai is written beside the sorted BAM: a BAI index (SAMv1
+                           //    5.2) whose rows are made on the device while each merged tile is still there (sg_bamindex_*; the
+                           //    rule: DESIGN.md "Index of the sorted truth BAM").  The BAM itself is byte for byte the same.  Refused
+                           //    without truth_sort, and for a contig longer than 2^29 bases
   int32_t truth_bam;       // 1: write every read's true alignment to <stem>.truth.bam beside the FASTQ files (sg_truth_bam: the
                            //    records are made and compressed on the device, piece by piece, in FASTQ order); needs the
                            //    device-assembled haplotypes (refused with host_haplotypes).  Sharded runs write parts like the
@@ -91,6 +95,10 @@ typedef struct simu_stats {
   int32_t emit_kernel;     // the emit kernels of the last pass (sg_emit_path: SG_EMIT_*; 0: no pass ran)
   int32_t emit_slow_rows_lds;
   uint32_t emit_lds_bytes, emit_clean_cap;
+  uint64_t bai_bins;       // truth_index: bins written to the .bai files (the pseudo-bins aside), ...
+  uint64_t bai_chunks;     // ... the chunks in them ...
+  uint64_t bai_bytes;      // ... and the files' bytes
+  double t_bai;            // sg_bamindex_* calls, simu_bai_build and writing the files (part of t_truth_sort)
   uint64_t truth_records;  // truth_bam: BAM records made (one per read), of which without an alignment ...
   uint64_t truth_unmapped;
   uint64_t truth_bytes;    // ... bytes of the record stream and of its BGZF members (header and end-of-file block aside)
@@ -171,6 +179,19 @@ uint64_t simu_variants_format(const char* const* contig_name, const uint64_t* co
 uint64_t simu_sort_tiles(uint32_t n_runs, const uint64_t* const* keys, const uint64_t* n, const uint64_t* const* prefix, uint64_t budget,
                          uint64_t* splitters, uint8_t* single, uint64_t cap);
 
+// The bytes of a --truth-index file (a BAI, SAMv1 5.2; the rule: csrc/sg_bamindex.h), host only.  rows: n_rows sg_bai_chunk
+// rows (simuscop_amd.h) -- the rows of all sg_bamindex_add calls of a stem in call order, every open end closed.  linear
+// and counts: what sg_bamindex_finish gives for the n_ref references of ref_len[] bases.  Rows are ordered by (refID,
+// bin) keeping their order within a bin, neighbours of a bin with end == beg are joined, bins are written ascending, the
+// pseudo-bin 37450 last for a reference with records (its end is the largest end of the reference's chunks), n_intv
+// reaches to the last touched window and an untouched window takes the value of the next touched one on its right;
+// n_no_coor closes the file.  The bytes are written to out[0 .. cap) when they fit; returns their number.  *bins = bins
+// written, the pseudo-bins aside, *chunks = chunks in them.  UINT64_MAX: tables that do not describe an index (a NULL
+// table, a row of a reference or bin that does not exist, an open end, rows and counts that disagree on whether a
+// reference has records).
+uint64_t simu_bai_build(uint32_t n_ref, const uint64_t* ref_len, const void* rows, uint64_t n_rows, const uint64_t* linear, const uint64_t* counts,
+                        void* out, uint64_t cap, uint64_t* bins, uint64_t* chunks);
+
 // ---- step-by-step session (bench.py / multi-GPU launcher) ----
 typedef struct simu_session simu_session;
 int simu_open(const char* config_path, const simu_options* opt, simu_session** out, char* err, size_t err_len);
@@ -201,6 +222,7 @@ inline std::string simu_truth_refusal(const simu_options& o, bool sharded, bool 
                         {"--truth-variants", o.truth_variants, false, true, "counts"}, {"--truth-errors", o.truth_errors, false, false, "tables"}};
   if (o.truth_tags && !o.truth_bam) return "Error: --truth-tags needs --truth-bam: the tags go on the truth BAM's records";
   if (o.truth_sort && !o.truth_bam) return "Error: --truth-sort needs --truth-bam: it is the truth BAM's records that are sorted";
+  if (o.truth_index && !o.truth_sort) return "Error: --truth-index needs --truth-sort: a BAI indexes a coordinate-sorted BAM";
   if (o.truth_sort && sharded)
     return "Error: --truth-sort cannot be combined with --world or --gpus above 1: the ranks' sorted parts would have to be merged, not "
            "concatenated";

@@ -26,10 +26,15 @@ void TruthSort::drop() {
   path.clear();
   runs.clear();
   spool_bytes = 0;
+  rows.clear();
+  open_row = SIZE_MAX;
+  rec_left = stage_skip = 0;
+  stage_lens.clear();
 }
 
 void TruthSort::open(const std::string& bam_path) {
   drop();
+  this->bam_path = bam_path;
   path = bam_path + ".runs.tmp";
   spool = fopen(path.c_str(), "w+b");
   if (!spool) {
@@ -78,8 +83,83 @@ void TruthSort::flush_stage(FILE* bam) {
     rc = sg_deflate_bgzf(eng.ctx, stage.data(), stage.size(), members.data(), members.size(), &n);
   }
   eng.check(rc, "sg_deflate_bgzf");
+  if (indexing) {
+    Timed acc{st.t_bai};
+    uint64_t nc = 0, fv = 0;
+    eng.check(sg_bamindex_add(eng.ctx, SG_BAMINDEX_DEFLATE, file_at, stage_skip, stage_lens.data(), stage_lens.size(), &nc, &fv), "sg_bamindex_add");
+    index_added(nc, fv);
+    stage_skip = rec_left;   // the record cut by this flush ends at the next stage's front
+    stage_lens.clear();
+  }
   put_members(bam, members.data(), n);
+  file_at += n;
   stage.clear();
+}
+
+void TruthSort::stage_from_run(const Run& run, uint64_t& rec, uint64_t bytes) {
+  while (bytes) {
+    if (!rec_left) {
+      rec_left = run.lens[rec++];
+      stage_lens.push_back((uint32_t)rec_left);
+    }
+    const uint64_t c = std::min(rec_left, bytes);
+    rec_left -= c;
+    bytes -= c;
+  }
+}
+
+void TruthSort::index_added(uint64_t n_chunks, uint64_t first_voff) {
+  if (open_row != SIZE_MAX && first_voff != ~0ull) {
+    rows[open_row].end = first_voff;
+    open_row = SIZE_MAX;
+  }
+  const size_t old = rows.size();
+  rows.resize(old + n_chunks);
+  uint64_t n = 0;
+  eng.check(sg_bamindex_chunks(eng.ctx, rows.data() + old, n_chunks, &n), "sg_bamindex_chunks");
+  for (size_t i = old; i < rows.size(); i++)
+    if (rows[i].end == ~0ull) open_row = i;
+}
+
+// the .bai goes with its owner unless it was written whole
+namespace {
+struct BaiFile {
+  std::string path;
+  FILE* f = nullptr;
+  bool whole = false;
+  ~BaiFile() {
+    if (f) fclose(f);
+    if (!whole && !path.empty()) unlink(path.c_str());
+  }
+};
+}  // namespace
+
+void TruthSort::write_index() {
+  Timed acc{st.t_bai};
+  if (open_row != SIZE_MAX) rows[open_row].end = file_at << 16;   // the end-of-file block follows
+  open_row = SIZE_MAX;
+  uint64_t n_win = 0;
+  for (uint64_t ln : ref_len) n_win += (ln + 16383) >> 14;
+  std::vector<uint64_t> linear(n_win + 1), counts(3 * ref_len.size() + 1);
+  eng.check(sg_bamindex_finish(eng.ctx, linear.data(), n_win, counts.data()), "sg_bamindex_finish");
+  uint64_t bins = 0, chunks = 0;
+  const uint64_t need = simu_bai_build((uint32_t)ref_len.size(), ref_len.data(), rows.data(), rows.size(), linear.data(), counts.data(), nullptr, 0,
+                                       &bins, &chunks);
+  if (need == UINT64_MAX) throw Error("Error: the index rows of the sorted truth BAM do not describe an index", -1);
+  std::vector<uint8_t> bai(need);
+  simu_bai_build((uint32_t)ref_len.size(), ref_len.data(), rows.data(), rows.size(), linear.data(), counts.data(), bai.data(), need, &bins, &chunks);
+  BaiFile out;
+  out.path = bam_path + ".bai";
+  out.f = fopen(out.path.c_str(), "wb");
+  if (!out.f) throw Error("Error: can not open the index file of the sorted truth BAM:\n" + out.path, -1);
+  const bool ok = fwrite(bai.data(), 1, bai.size(), out.f) == bai.size();
+  const bool closed = fclose(out.f) == 0;
+  out.f = nullptr;
+  if (!ok || !closed) throw Error("Error: short write to the index file of the sorted truth BAM", -1);
+  out.whole = true;
+  st.bai_bins += bins;
+  st.bai_chunks += chunks;
+  st.bai_bytes += bai.size();
 }
 
 void TruthSort::finish(FILE* bam) {
@@ -92,6 +172,14 @@ void TruthSort::finish(FILE* bam) {
   const uint32_t R = (uint32_t)runs.size();
   st.truth_sort_runs += R;
   st.truth_spool_bytes += spool_bytes;
+  if (indexing) {
+    Timed acc{st.t_bai};
+    unlink((bam_path + ".bai").c_str());   // (an index of an earlier run does not outlive a failure of this one)
+    const off_t at = ftello(bam);
+    if (at < 0) throw Error("Error: can not tell where the truth BAM's records start", -1);
+    file_at = (uint64_t)at;
+    eng.check(sg_bamindex_begin(eng.ctx, (uint32_t)ref_len.size(), ref_len.data()), "sg_bamindex_begin");
+  }
   if (R) {
     if (fflush(spool) != 0) throw Error("Error: short write to the spool file of the sorted truth BAM", -1);
     std::vector<std::vector<uint64_t>> prefix(R);
@@ -125,13 +213,14 @@ void TruthSort::finish(FILE* bam) {
       }
       if (T.single[t]) {   // one key value: the merged order is the runs in order, nothing to sort
         for (uint32_t r = 0; r < R; r++) {
-          uint64_t at = runs[r].at + prefix[r][a[r]], left = part_bytes[r];
+          uint64_t at = runs[r].at + prefix[r][a[r]], left = part_bytes[r], rec = a[r];
           while (left) {
             if (stage.size() >= chunk) flush_stage(bam);
             const uint64_t take = std::min<uint64_t>(left, chunk - stage.size());
             const size_t old = stage.size();
             stage.resize(old + take);
             read_spool(at, take, stage.data() + old);
+            if (indexing) stage_from_run(runs[r], rec, take);
             at += take;
             left -= take;
           }
@@ -153,12 +242,20 @@ void TruthSort::finish(FILE* bam) {
         if (ob != tile_bytes) throw Error("Error: a merged tile of the truth BAM has another size than its runs", -1);
         if (members.size() < gb) members.resize(gb);
         eng.check(sg_bamsort_fetch(eng.ctx, 1, 0, gb, members.data()), "sg_bamsort_fetch");
+        if (indexing) {
+          Timed acc{st.t_bai};
+          uint64_t nc = 0, fv = 0;
+          eng.check(sg_bamindex_add(eng.ctx, SG_BAMINDEX_MERGE, file_at, 0, nullptr, 0, &nc, &fv), "sg_bamindex_add");
+          index_added(nc, fv);
+        }
         put_members(bam, members.data(), gb);
+        file_at += gb;
       }
       a = b;
     }
     flush_stage(bam);
   }
+  if (indexing) write_index();
   st.t_truth_sort += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 

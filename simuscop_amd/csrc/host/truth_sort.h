@@ -39,6 +39,10 @@ class TruthSort {
   void open(const std::string& bam_path);   // a stem starts: <bam_path>.runs.tmp
   void add_run(uint64_t record_bytes);      // the pass sg_bamsort_pass has just made: its stream to the spool, its index to memory
   void finish(FILE* bam);                   // the stem ends: tiles, merges, members appended to `bam`; the spool is removed
+  // --truth-index: every later stem's finish() also writes <bam_path>.bai (the rule: csrc/sg_bamindex.h).  Each compressed
+  // text is indexed on the device while it is still there (sg_bamindex_add), behind the merge or the pass-through chunk
+  // that made it; nothing about the BAM's bytes changes.
+  void index_with(const std::vector<uint64_t>& lens) { indexing = true; ref_len = lens; }
 
  private:
   struct Run {
@@ -50,9 +54,19 @@ class TruthSort {
   void read_spool(uint64_t at, uint64_t bytes, uint8_t* dst);
   void put_members(FILE* bam, const uint8_t* p, uint64_t n);
   void flush_stage(FILE* bam);
+  void stage_from_run(const Run& run, uint64_t& rec, uint64_t bytes);   // `bytes` more of the run's records are staged, from record `rec` on
+  void index_added(uint64_t n_chunks, uint64_t first_voff);            // the rows of the sg_bamindex_add just made
+  void write_index();
+  bool indexing = false;
+  std::vector<uint64_t> ref_len;
+  std::vector<sg_bai_chunk> rows;   // the stem's chunk rows in call order
+  size_t open_row = SIZE_MAX;       // the one whose end the next call's first record closes
+  uint64_t file_at = 0;             // where the next member lands in the BAM file
+  uint64_t rec_left = 0, stage_skip = 0;   // pass-through: bytes of the record being staged still to come; those at the stage's front that belong to an earlier one
+  std::vector<uint32_t> stage_lens;        // ... lengths of the records that start in the stage
   Engine& eng;
   simu_stats& st;
-  std::string path;
+  std::string path, bam_path;
   FILE* spool = nullptr;
   uint64_t spool_bytes = 0;
   std::vector<Run> runs;

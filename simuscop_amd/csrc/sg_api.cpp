@@ -821,6 +821,7 @@ uint32_t sg_deflate_plan(const uint64_t lit_counts[286], const uint64_t dist_cou
 // (declared in sg_api.h, not part of the ABI)
 extern "C++" int deflate_text(sg_ctx* ctx, const uint8_t* text, uint64_t bytes, DevBuf& gz, uint64_t* gz_total, const char* who) {
   hipStream_t s = ctx->stream;
+  ctx->gz_last = sg_ctx::GzLast();
   if (bytes / sg::kGzChunk >= 0xFFFFFFF0ull) return ctx->fail(SG_ERR_UNSUPPORTED, std::string(who) + ": text too large");
   const uint32_t n_chunks = (uint32_t)((bytes + sg::kGzChunk - 1) / sg::kGzChunk);
   // work buffer: hist[320] u64 | total u64 | counters | tables | msize[n] u32 | moff[n] u64 | block sums | lane bits | records
@@ -910,6 +911,9 @@ extern "C++" int deflate_text(sg_ctx* ctx, const uint8_t* text, uint64_t bytes, 
   SG_HIP(hipGetLastError());
   SG_HIP(hipStreamSynchronize(s));  // tab / plan are host-owned
   *gz_total = total;
+  ctx->gz_last.text = text;
+  ctx->gz_last.bytes = bytes;
+  ctx->gz_last.moff = D.moff;
   return SG_OK;
 }
 

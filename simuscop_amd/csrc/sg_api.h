@@ -1,7 +1,7 @@
 // sg_api.h -- what the files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
 // sink, reference, haplotypes), sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM
 // input), sg_api_depth.cpp (true coverage), sg_api_variants.cpp (true allele counts) and sg_api_errors.cpp (true error
-// counts) and sg_api_bamsort.cpp (the truth BAM in coordinate order).  Internal: the ABI itself is include/simuscop_amd.h.
+// counts), sg_api_bamsort.cpp (the truth BAM in coordinate order) and sg_api_bamindex.cpp (its BAI index).  Internal: the ABI itself is include/simuscop_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -114,7 +114,28 @@ struct sg_ctx {
     int cur = 0;
     uint64_t n = 0, out_bytes = 0, gz_bytes = 0;
     DevBuf keys[2], vals[2], lens, work, src, out, gz;
+    const uint64_t* dst_off = nullptr;   // of a merge: where its records start in `out` (in `work`, until the next sg_bamsort_* call)
   } bamsort;
+  // The last compression (deflate_text): its text and the member offset table it left in gz_work -- entry i is where the
+  // member of text bytes [32768 i, 32768 i + 32768) starts among the members.  Forgotten when the next one starts.
+  struct GzLast {
+    const uint8_t* text = nullptr;
+    uint64_t bytes = 0;
+    const uint64_t* moff = nullptr;
+  } gz_last;
+  // the BAI index of the sorted truth BAM (sg_bamindex_*, sg_api_bamindex.cpp; the index: sg_bamindex.h): of the stem the
+  // references (`refs`: sg::BaiRef rows), the linear index and the counts; of a call its rows, offsets, chunk rows
+  // (`work`, `chunks`) and the (key, chunk number) pairs of their sort; `carry` holds a record that a text of
+  // sg_deflate_bgzf left unfinished, until the next text brings its rest.  Without sg_bamindex_begin nothing is kept and
+  // nothing is allocated.
+  struct BamIndex {
+    bool on = false, broken = false;
+    std::vector<uint64_t> ref_len;
+    uint64_t n_win = 0, n_chunks = 0, carry_voff = 0;
+    uint32_t carry_have = 0, carry_need = 0;   // bytes of the unfinished record in `carry`, and those still to come
+    int cur = 0;
+    DevBuf refs, linear, counts, work, chunks, keys[2], vals[2], carry;
+  } bamindex;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // the window planner (sg_gc_percent, sg_window_weights, sg_windows_*, sg_plan_windows / sg_plan_range;
   // sg_api_windows.cpp): `stores` holds the window weights of sg_windows_build per store id, `plan` the batch table of
@@ -228,6 +249,19 @@ int sg_pass_records(sg_ctx* ctx, const char* who, uint32_t tags, bool sorted, ui
 namespace sg { struct TruthJob; }
 int bamsort_pass_keys(sg_ctx* ctx, const sg::TruthJob& J, bool paired);
 int bamsort_pass_order(sg_ctx* ctx, const sg::TruthJob& J, uint64_t* rec_off, uint64_t* total);
+// The stable sort of n (u64 key, u32 payload) pairs in keys[*cur] / vals[*cur] (sg_api_bamsort.cpp); the result is in
+// keys[*cur] / vals[*cur] again.  A digit in which k_or and k_and agree is the same in all keys and is skipped.  hist and
+// hist_off hold 256 * bamsort_blocks(n) cells, bsum what launch_scan_u32 asks for that many values, *total one cell.
+struct SgSortBufs {
+  DevBuf* keys;   // [2]
+  DevBuf* vals;   // [2]
+  int* cur;
+  uint32_t* hist;
+  uint64_t* hist_off;
+  uint64_t* bsum;
+  uint64_t* total;
+};
+int bamsort_sort_pairs(sg_ctx* ctx, const SgSortBufs& b, uint32_t n, uint64_t k_or, uint64_t k_and);
 // no context, or a call in front of its output's X_begin
 inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
   if (!ctx) return SG_ERR_INVALID;

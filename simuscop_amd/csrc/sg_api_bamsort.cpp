@@ -47,19 +47,7 @@ int carve_work(sg_ctx* ctx, uint32_t n, bool pass, bool merge, SortWork* W) {
 // and the AND of the keys agree on it) moves nothing and is skipped.
 int sort_pairs(sg_ctx* ctx, const SortWork& W, uint32_t n, uint64_t k_or, uint64_t k_and) {
   sg_ctx::BamSort& S = ctx->bamsort;
-  if (n < 2) return SG_OK;
-  const uint32_t n_hist = sg::kSortDigits * sg::bamsort_blocks(n);
-  for (uint32_t shift = 0; shift < 64; shift += 8) {
-    if ((((k_or ^ k_and) >> shift) & 255u) == 0) continue;
-    const int from = S.cur, to = S.cur ^ 1;
-    sg::launch_bamsort_hist(S.keys[from].as<uint64_t>(), n, shift, W.hist, ctx->stream);
-    sg::launch_scan_u32(W.hist, n_hist, W.bsum, W.hist_off, (uint64_t*)&W.counters[7], ctx->stream);
-    sg::launch_bamsort_scatter(S.keys[from].as<uint64_t>(), S.vals[from].as<uint32_t>(), n, shift, W.hist_off, S.keys[to].as<uint64_t>(),
-                               S.vals[to].as<uint32_t>(), ctx->stream);
-    S.cur = to;
-  }
-  SG_HIP(hipGetLastError());
-  return SG_OK;
+  return bamsort_sort_pairs(ctx, SgSortBufs{S.keys, S.vals, &S.cur, W.hist, W.hist_off, W.bsum, (uint64_t*)&W.counters[7]}, n, k_or, k_and);
 }
 
 int ensure_pairs(sg_ctx* ctx, uint32_t n) {
@@ -74,10 +62,27 @@ int ensure_pairs(sg_ctx* ctx, uint32_t n) {
 
 }  // namespace
 
+int bamsort_sort_pairs(sg_ctx* ctx, const SgSortBufs& b, uint32_t n, uint64_t k_or, uint64_t k_and) {
+  if (n < 2) return SG_OK;
+  const uint32_t n_hist = sg::kSortDigits * sg::bamsort_blocks(n);
+  for (uint32_t shift = 0; shift < 64; shift += 8) {
+    if ((((k_or ^ k_and) >> shift) & 255u) == 0) continue;
+    const int from = *b.cur, to = *b.cur ^ 1;
+    sg::launch_bamsort_hist(b.keys[from].as<uint64_t>(), n, shift, b.hist, ctx->stream);
+    sg::launch_scan_u32(b.hist, n_hist, b.bsum, b.hist_off, b.total, ctx->stream);
+    sg::launch_bamsort_scatter(b.keys[from].as<uint64_t>(), b.vals[from].as<uint32_t>(), n, shift, b.hist_off, b.keys[to].as<uint64_t>(),
+                               b.vals[to].as<uint32_t>(), ctx->stream);
+    *b.cur = to;
+  }
+  SG_HIP(hipGetLastError());
+  return SG_OK;
+}
+
 int bamsort_pass_keys(sg_ctx* ctx, const sg::TruthJob& J, bool paired) {
   sg_ctx::BamSort& S = ctx->bamsort;
   const uint32_t N = J.map.n_reads;
   S.have = false;
+  S.dst_off = nullptr;
   S.n = S.out_bytes = S.gz_bytes = 0;
   S.cur = 0;
   SortWork W;
@@ -134,6 +139,7 @@ int sg_bamsort_merge(sg_ctx* ctx, uint32_t n_runs, const void* const* records, c
   if (n_runs && (!records || !record_bytes || !keys || !lens || !n)) return ctx->fail(SG_ERR_INVALID, "sg_bamsort_merge: null run tables");
   sg_ctx::BamSort& S = ctx->bamsort;
   S.have = false;
+  S.dst_off = nullptr;
   S.n = S.out_bytes = S.gz_bytes = 0;
   S.cur = 0;
   ctx->pass.bam_sorted = false;   // the index is this call's from here on
@@ -189,6 +195,7 @@ int sg_bamsort_merge(sg_ctx* ctx, uint32_t n_runs, const void* const* records, c
     if (c[0] != total_b || (c[1] & 1)) return ctx->fail(SG_ERR_INVALID, "sg_bamsort_merge: a record outside the stream");
     if (total_b)
       if (int rc = deflate_text(ctx, S.out.as<uint8_t>(), total_b, S.gz, &S.gz_bytes, "sg_bamsort_merge")) return rc;
+    S.dst_off = W.dst_off;
   }
   S.n = N;
   S.out_bytes = total_b;
