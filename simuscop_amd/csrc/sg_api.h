@@ -1,7 +1,13 @@
-// sg_api.h -- what the files of the C ABI share: sg_api.cpp (context, profile tables, sampling pass, outputs, BGZF
-// sink, reference, haplotypes), sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM
-// input), sg_api_depth.cpp (true coverage), sg_api_variants.cpp (true allele counts) and sg_api_errors.cpp (true error
-// counts), sg_api_bamsort.cpp (the truth BAM in coordinate order) and sg_api_bamindex.cpp (its BAI index).  Internal: the ABI itself is include/simuscop_amd.h.
+// sg_api.h -- what the files of the C ABI share.  Internal: the ABI itself is include/simuscop_amd.h.  Who defines what:
+//   sg_memory.cpp          block and pinned-memory caches: DevBuf::ensure / release, sg_host_alloc / _free, sg_release_cached_memory
+//   sg_api.cpp             the context, sg_load_profile / sg_load_prepared_profile, sg_plan and finish_plan, the sampling pass
+//                          (sg_sample, sg_pass_need, retire_plan), sg_result and the fetch calls, detached outputs
+//   sg_profile_tables.cpp  sg_profile_prepare and the table self-checks (host only: sg_profile_tables.h)
+//   sg_api_deflate.cpp     the BGZF sink: deflate_text, sg_compress, sg_deflate_bgzf, sg_fetch_compressed, sg_bgzf_eof
+//   sg_api_truth.cpp       truth alignments and the truth BAM: sg_pass_prelude, sg_truth_*, sg_pass_records, sg_fetch_truth
+//   sg_api_haplotypes.cpp  reference ingest and haplotype assembly: sg_reference_*, sg_build / upload_haplotypes, sg_haplotype_codes
+//   sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM input), sg_api_depth.cpp / _variants.cpp /
+//   _errors.cpp (true coverage, allele and error counts), sg_api_bamsort.cpp / _bamindex.cpp (the sorted truth BAM, its BAI index)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,7 +19,7 @@
 #include "sg_device.h"
 #include "sg_haplotypes.h"
 
-// A grow-only device buffer that owns its block.  The block goes back to the process's block cache (sg_api.cpp) when the
+// A grow-only device buffer that owns its block.  The block goes back to the process's block cache (sg_memory.cpp) when the
 // buffer is destroyed, released or assigned over; the cache waits for the device first, so nothing still queued can touch
 // the block once it is handed out again.  Move-only: a move hands the block over.
 struct DevBuf {
@@ -34,6 +40,12 @@ struct DevBuf {
   template <class T> T* as() const { return (T*)p; }
 };
 
+// One pass's output buffers by mate: the FASTQ text, its BGZF members (sg_compress).  Handing a set over is one std::swap.
+struct OutputSet {
+  DevBuf text[2], gz[2];
+  bool empty() const { return !text[0].p && !text[1].p && !gz[0].p && !gz[1].p; }
+};
+
 extern thread_local std::string g_create_error;   // sg_last_error(nullptr): calls without a context
 
 struct sg_outputs;
@@ -49,8 +61,9 @@ struct sg_ctx {
   bool have_profile = false, have_haps = false;   // the inputs; everything about a batch and its pass is in `pass`
   sg::DevProfile P{};
   sg::DevBatch B{};
+  OutputSet out;
   DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_actual, win_namebase, events, recoff, meta, totals, bsum,
-      out1, out2, slowq, ref_raw, ref_codes, ref_meta, hap_work, gz1, gz2, gz_work,
+      slowq, ref_raw, ref_codes, ref_meta, hap_work, gz_work,
       infl_src, infl_meta, infl_out, infl_crc,   // sg_inflate_bgzf (infl_crc also serves the training session's BAM input)
       defl_src, defl_out;                        // sg_deflate_bgzf: the caller's text and its members
   // the haplotype chains in `chains` (sg_upload_haplotypes, sg_build_haplotypes): chain c holds len[c] bases from off[c] on;
@@ -163,7 +176,7 @@ struct sg_ctx {
   std::vector<sg::DevContig> ref_contigs;  // host copy of the committed contig table
   uint64_t* mail = nullptr;   // pinned: where a pass's totals[0..4] land (copied into `pass` when it is settled)
   // A batch and its sampling pass: the stage, and every fact whose meaning ends with the pass.  The buffers those facts
-  // describe stay where they are (out1 / out2, gz1 / gz2, truth.rec / truth.gz).  Starting over is assigning a fresh Pass.
+  // describe stay where they are (out.text / out.gz, truth.rec / truth.gz).  Starting over is assigning a fresh Pass.
   //
   //   None --sg_plan*--> Planned --sg_sample--> Queued --sg_pass_need(.., Settled, true)--> Settled
   //
@@ -188,7 +201,7 @@ struct sg_ctx {
     uint64_t slow_items = 0;
     bool slow_overflow = false;
     sg::EmitPath emit_path = {0, -1, 0, 0};  // the emit kernels of the pass (sg_emit_path)
-    bool have_gz = false;             // sg_compress: gz1 / gz2 hold gz_bytes of members
+    bool have_gz = false;             // sg_compress: out.gz holds gz_bytes of members
     uint64_t gz_bytes[2] = {0, 0};
     bool have_bam = false;            // sg_truth_bam: truth.rec / truth.gz hold the pass's records
     bool bam_sorted = false;          // ... made by sg_bamsort_pass: in key order, uncompressed, indexed by ctx->bamsort
@@ -225,7 +238,7 @@ namespace sg { struct PieceMap; }
 // The start of a call that reads the rows of the pass just sampled, its checks in this order: rows that still belong to
 // the chains and the profile; with `map`, the chains' piece map (sg_build_haplotypes, then sg_truth_map); sg_result; with
 // `map`, fewer than 2^32 reads; with `bam_names`, read names that a BAM record holds (sg_truth_bam's own check, whose
-// place is in front of the next); no SG_DIAG.  The device is selected and *map filled.  Defined in sg_api.cpp.
+// place is in front of the next); no SG_DIAG.  The device is selected and *map filled.  Defined in sg_api_truth.cpp.
 int sg_pass_prelude(sg_ctx* ctx, const char* who, sg::PieceMap* map, bool bam_names = false);
 // The gate of every call that reads a pass: no context; "<who>: call sg_plan / sg_sample / sg_result first" when the
 // stage is below `at_least`; then the device is selected.  Settled is asked in two ways: of a pass that sg_result has
@@ -236,12 +249,14 @@ int sg_pass_need(sg_ctx* ctx, const char* who, sg_ctx::Pass::Stage at_least, boo
 // of sg_plan and sg_plan_range.  Internal like the two above, not part of the ABI.  Defined in sg_api.cpp.
 int finish_plan(sg_ctx* ctx, uint64_t nw, uint32_t n_segs, uint32_t n_slots, uint32_t batch_id, uint32_t first_window,
                 uint32_t first_slot, int32_t paired, const char* name_prefix);
+// The chains or the profile changed: the plan is gone, and a pass's rows no longer belong to them (its text stays).
+void retire_plan(sg_ctx* ctx);
 // `bytes` (> 0) of text on the device -> its BGZF members in `gz`, *gz_total bytes of them.  `text` is followed by 64
 // readable bytes, as the sampler's output buffers are.  What sg_compress does per mate, sg_deflate_bgzf for its caller,
-// sg_truth_bam for its records and sg_bamsort_merge for its stream.  Defined in sg_api.cpp.
+// sg_truth_bam for its records and sg_bamsort_merge for its stream.  Defined in sg_api_deflate.cpp.
 int deflate_text(sg_ctx* ctx, const uint8_t* text, uint64_t bytes, DevBuf& gz, uint64_t* gz_total, const char* who);
 // The records of the pass just sampled into truth.rec (sg_truth_bam_tags; `sorted`: sg_bamsort_pass, whose stream is in
-// key order and stays uncompressed).  Defined in sg_api.cpp.
+// key order and stays uncompressed).  Defined in sg_api_truth.cpp.
 int sg_pass_records(sg_ctx* ctx, const char* who, uint32_t tags, bool sorted, uint64_t* record_bytes, uint64_t* bgzf_bytes);
 // The two steps sg_pass_records takes for a sorted pass (sg_api_bamsort.cpp).  bamsort_pass_keys, behind the sizing
 // kernels on the stream: the live records' keys.  bamsort_pass_order, once the stream has been waited for: sorts them and
@@ -275,6 +290,15 @@ inline int sg_read_back(sg_ctx* ctx, void* dst, const void* src, size_t bytes) {
   SG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   return SG_OK;
+}
+// [offset, offset + bytes) lies within `have` bytes.  (The sum is never formed: it wraps for a large offset.)
+inline bool sg_range_within(uint64_t offset, uint64_t bytes, uint64_t have) { return offset <= have && bytes <= have - offset; }
+// `bytes` of device memory at `src` (the caller has tested the range), on the host when this returns hipSuccess
+inline hipError_t sg_fetch_bytes(int device, hipStream_t stream, void* dst, const void* src, uint64_t bytes) {
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && bytes) e = hipStreamSynchronize(stream);
+  return e;
 }
 // Zero n (<= 8) counters, launch, read them back.
 template <class Launch>

@@ -1,6 +1,6 @@
 // sg_api_bamsort.cpp -- sg_bamsort_*: the truth BAM in coordinate order (simuReads --truth-sort).  The order is stated in
 // sg_bamsort.h, the kernels are in sg_bamsort.hip.  A pass comes out sorted because the pack kernels write each record
-// at rec_off[read], and rec_off here is the scan of the lengths taken in key order (sg_pass_records, sg_api.cpp); the
+// at rec_off[read], and rec_off here is the scan of the lengths taken in key order (sg_pass_records, sg_api_truth.cpp); the
 // sorted passes of a stem are merged by sorting their concatenation again (sg_bamsort_merge), which needs no pass, no
 // profile and no piece map.
 #include <algorithm>

@@ -56,29 +56,6 @@ Row encode_row(const double* cdf, int ac) {
   return r;
 }
 
-CompactRow encode_compact_row(const double* cdf, int ac) {
-  CompactRow r;
-  Row full = encode_row(cdf, ac);
-  for (size_t i = 0; i < full.T.size(); i++) {
-    if (i > 0 && full.T[i] == full.T[i - 1]) continue;  // zero mass: never the first hit
-    r.T.push_back(full.T[i]);
-    r.sym.push_back((uint8_t)(full.k0 + i));
-  }
-  return r;
-}
-
-void encode_sub_row(const double* cdf4, uint32_t out[4]) {
-  uint64_t cnt[4];
-  int k0 = -1;
-  for (int k = 0; k < 4; k++) {
-    cnt[k] = count_le(cdf4[k]);
-    if (k0 < 0 && cnt[k] >= 1) k0 = k;
-  }
-  if (k0 < 0) k0 = 3;
-  for (int k = 0; k < 3; k++) out[k] = (k < k0) ? 0u : (uint32_t)(cnt[k] - 1);
-  out[3] = (uint32_t)k0;
-}
-
 std::vector<uint64_t> row_masses(const double* cdf, int ac) {
   std::vector<uint64_t> n((size_t)ac, 0);
   uint64_t prev = 0;

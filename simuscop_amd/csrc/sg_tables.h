@@ -9,7 +9,8 @@
 //     T[i] = count_le(cdf[k0+i]) - 1      ("x <= T[i]"),  last kept entry forced to 0xFFFFFFFF,
 // padded with 0xFFFFFFFF to a power-of-two width so that the lookup is a branch-free lower bound:
 //     k = k0 + #{i : x > T[i]}.
-// This reproduces randIndx for every one of the 2^32 possible draws (tests/test_tables.py).
+// This reproduces randIndx for every one of the 2^32 possible draws (tests/test_tables_and_abi.py,
+// tests/test_integer_tables.py).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -28,18 +29,6 @@ struct Row {
   std::vector<uint32_t> T;  // kept thresholds, T.back() == 0xFFFFFFFF
 };
 Row encode_row(const double* cdf, int ac);
-
-// Compact row: entries that can never be chosen (zero probability mass, i.e. the same count as their
-// predecessor) are dropped -- if x <= T[k] == T[k-1] then k-1 is found first -- and every kept entry
-// remembers which original index it stands for:  k = sym[#{i : x > T[i]}].  Exact for all 2^32 draws.
-struct CompactRow {
-  std::vector<uint32_t> T;    // strictly increasing, T.back() == 0xFFFFFFFF
-  std::vector<uint8_t> sym;   // original index of each kept entry
-};
-CompactRow encode_compact_row(const double* cdf, int ac);
-
-// Substitution row (N = 4): {T0, T1, T2, k0};  k = max(k0, (x>T0)+(x>T1)+(x>T2)).
-void encode_sub_row(const double* cdf4, uint32_t out[4]);
 
 // ---- measure-preserving rearrangements used by the per-base sampling ----
 // A CDF row of `ac` entries partitions the 2^32 draws: outcome k < ac-1 gets count_le(cdf[k]) - count_le(cdf[k-1])
@@ -67,24 +56,10 @@ struct AliasRow {
 uint32_t symbols_with_mass(const std::vector<uint64_t>& masses);
 AliasRow build_alias_row(const std::vector<uint64_t>& masses, uint32_t lgW);  // throws std::runtime_error if masses do not fit
 
-inline uint32_t pow2_at_least(uint32_t n) {
-  uint32_t p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-inline uint32_t log2u(uint32_t p) {
+inline uint32_t log2_at_least(uint32_t n) {   // the smallest l with 2^l >= n
   uint32_t l = 0;
-  while ((1u << l) < p) l++;
+  while ((1u << l) < n) l++;
   return l;
-}
-
-// Host mirror of the device lookup (used by tests and by the ABI self-check).
-inline uint32_t row_lookup(const uint32_t* row, uint32_t lg, uint32_t x) {
-  const uint32_t* T = row + 1;
-  uint32_t pos = 0;
-  for (uint32_t step = lg ? (1u << (lg - 1)) : 0; step; step >>= 1)
-    if (x > T[pos + step - 1]) pos += step;
-  return row[0] + pos;
 }
 
 }  // namespace sg

@@ -15,6 +15,8 @@ from simuscop_amd import synth
 
 pytestmark = pytest.mark.gpu
 
+SG_ERR_INVALID = 1   # include/simuscop_amd.h
+
 
 @pytest.fixture(scope="module")
 def eng():
@@ -211,6 +213,45 @@ def test_detached_outputs_survive_the_next_pass(tmp_path):
         sess.close()
 
 
+def test_fetch_ranges_that_wrap_are_refused(tmp_path):
+    """offset + bytes wraps past 2^64 for a large offset: the ranged fetch calls refuse such a range like any other past
+    the end (none copies from in front of its buffer), with their own messages, and the pass stays fetchable."""
+    cfg = cases.build_case("wgs_pe_xten", str(tmp_path))
+    sess = simuscop_amd.Session(cfg, device=0, write_files=0, quiet=1, seed=21)
+    eng = sess.eng
+    try:
+        sess.weighted_length()
+        sess.set_reads(sess.planned_reads)
+        assert sess.prepare_batch(0)
+        sess.sample()
+        b1, b2, nf = sess.result()
+        g1, g2 = sess.compress()
+        assert min(b1, b2, g1, g2) >= 16
+        off, n = 2 ** 64 - 8, 16
+        buf = C.create_string_buffer(n)
+        for mate in (0, 1):
+            assert eng.sg_fetch_range(sess.ctx, mate, off, n, buf) == SG_ERR_INVALID
+            assert eng.sg_last_error(sess.ctx) == b"sg_fetch_range: range past the end of the FASTQ text"
+            assert eng.sg_fetch_compressed(sess.ctx, mate, off, n, buf) == SG_ERR_INVALID
+            assert eng.sg_last_error(sess.ctx) == b"sg_fetch_compressed: range past the end of the compressed text"
+        assert buf.raw == bytes(n)
+        assert eng.sg_fetch_range(sess.ctx, 0, 0, n, buf) == 0, eng.sg_last_error(sess.ctx)
+        head = buf.raw
+        assert head.startswith(b"@")
+        h = C.c_void_p()
+        assert eng.sg_detach_outputs(sess.ctx, C.byref(h)) == 0
+        got = C.create_string_buffer(n)
+        for mate in (0, 1):
+            for compressed in (0, 1):
+                assert eng.sg_outputs_fetch(h, mate, compressed, off, n, got) == SG_ERR_INVALID
+                assert eng.sg_outputs_last_error(h) == b"sg_outputs_fetch: range past the end of the data"
+        assert got.raw == bytes(n)
+        assert eng.sg_outputs_fetch(h, 0, 0, 0, n, got) == 0 and got.raw == head
+        assert eng.sg_release_outputs(sess.ctx, h) == 0
+    finally:
+        sess.close()
+
+
 def test_a_pass_larger_than_the_buffers_it_was_launched_into(tmp_path, monkeypatch):
     """Every pass but a context's first is queued without waiting for the text size (the emit kernels are launched into
     the buffers the context holds and check the capacity themselves).  A small chromosome first, then the largest one:
@@ -243,7 +284,7 @@ def test_a_pass_larger_than_the_buffers_it_was_launched_into(tmp_path, monkeypat
 
 
 def test_runs_in_one_process_reuse_device_blocks(tmp_path):
-    """The device blocks a finished run gave up serve the next run of the process (sg_api.cpp BlockCache; what keeps a
+    """The device blocks a finished run gave up serve the next run of the process (sg_memory.cpp BlockCache; what keeps a
     sequence of whole-genome runs off the allocator, see tools/c3_steps.py).  They come back dirty -- holding the other
     run's tables, rows and text -- so: the same configuration before and after a different one, and after the cache was
     emptied, must write the same bytes; so must a run with the cache turned off in a fresh process (the parity tests)."""

@@ -125,17 +125,31 @@ def test_records_equal_the_fastq(name, oracle_lib, tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. the device states the host rule
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["k3_b53_PE_fast_kernel", "k3_b52_SE_fast_kernel", "k5_b10_PE", "wgs_pe_variants", "wes_pe_targets"])
+# the smallest passes: one read, and 257 reads -- the scan of the record lengths takes 256 values a block
+FEW_READS = {"wgs_se_hs2000_1_read": 1, "wgs_se_hs2000_257_reads": 257}
+
+
+def _reads_that_give(sess, slots):
+    """the read count whose first chromosome's pass has exactly `slots` fragment slots"""
+    for reads in range(max(1, slots - 2), 2 * slots + 8):
+        sess.set_reads(reads)
+        if sess.prepare_batch(0) and sess.batch_slots == slots:
+            return reads
+    pytest.fail("no set_reads() value gives %d slots" % slots)
+
+
+@pytest.mark.parametrize("name", ["k3_b53_PE_fast_kernel", "k3_b52_SE_fast_kernel", "k5_b10_PE", "wgs_pe_variants", "wes_pe_targets"] + list(FEW_READS))
 def test_device_records_follow_the_host_rule(name, tmp_path):
     wd = str(tmp_path)
-    cfg = RUNS[name](wd)
+    few = FEW_READS.get(name)
+    cfg = cases.build_case("wgs_se_hs2000", wd) if few else RUNS[name](wd)
     paired = "layout = PE" in open(cfg).read()
     with simuscop_amd.Session(cfg, device=0, write_files=0, quiet=1, seed=SEED, truth_bam=1) as sess:
         L = None
         sess.weighted_length()
-        sess.set_reads(sess.planned_reads)
+        sess.set_reads(_reads_that_give(sess, few) if few else sess.planned_reads)
         checked = with_events = gapped = clipped = 0
-        for chrom in range(sess.n_chromosomes):
+        for chrom in range(1 if few else sess.n_chromosomes):
             if not sess.prepare_batch(chrom):
                 continue
             sess.sample()
@@ -174,7 +188,10 @@ def test_device_records_follow_the_host_rule(name, tmp_path):
                     gapped += any(o in (2, 3) for _, o in a[2])
                     clipped += any(o == 4 for _, o in a[2])
             assert next(it, None) is None
-        assert checked > 1000 and with_events > 20, (checked, with_events, gapped, clipped)
+        if few:
+            assert 0 < checked <= few
+        else:
+            assert checked > 1000 and with_events > 20, (checked, with_events, gapped, clipped)
         if name in ("wgs_pe_variants", "wes_pe_targets"):
             assert gapped > 0
 

@@ -213,7 +213,7 @@ def test_window_weights_equal_the_model_bit_for_bit(eng, lg_cells, full_tile_for
 def test_window_ending_on_the_last_byte_of_the_last_chain(eng):
     """gc_kernel loads 16 bytes at every 16th byte of a window, so the load of a window's tail reaches up to 15 bytes past
     the window: for a window that ends on the last chain's last byte, past the chains.  Settled by reading
-    sg_api.cpp: chain_layout (used by sg_upload_haplotypes and sg_build_haplotypes alike) puts a guard of 256 bytes in front
+    sg_api_haplotypes.cpp: chain_layout (used by sg_upload_haplotypes and sg_build_haplotypes alike) puts a guard of 256 bytes in front
     of every chain and behind the last one, rounds every chain up to 64 bytes and the whole buffer up to 1,024, and both
     routes fill the guards with N before the chains are copied in; the allocation is `total` bytes.  The load stays inside
     the allocation, and the kernel masks the bytes past the window off before it counts, so the guard's N do not count
