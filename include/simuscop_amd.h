@@ -767,6 +767,64 @@ int sg_sub_row_identity_first(const double cdf4[4], int cd, uint64_t cum[3], uin
 uint32_t sg_row_symbols(const double* cdf, int n);
 int sg_alias_row(const double* cdf, int n, uint32_t lgW, uint32_t* thr, uint8_t* lo, uint8_t* hi);
 
+/* ---- a VCF of known variants, read on the device: the rows lib/vcfparser/vcfparser.cpp:26-106 yields ----
+ * The text -- plain, or the members of a BGZF file as bgzip writes them -- is cut into the fragments the parser's
+ * fgets(buf, 20000) returns, and every fragment gets the parser's verdict: skipped, an SNV, an insertion or a deletion with
+ * the values the parser stores, malformed (fewer than ten fields), or UNDECIDED.  The rule and the exact set of forms
+ * decided on the device are stated in csrc/sg_vcf.h; an undecided fragment (an exponent in QUAL, over-long digit strings,
+ * white space in front of a number, a NUL byte) is handed back with its bytes for the caller to resolve.
+ *   sg_vcf_begin      a session on `n_contigs` contig keys (each shorter than 64 bytes; row = index), one per context
+ *   sg_vcf_feed       host text, cut anywhere: a line the call leaves unfinished stays on the device and leads the next one.
+ *                     At most 1 GiB per call; a line longer than 64 MiB, finished or not, is SG_ERR_INVALID naming its offset
+ *   sg_vcf_feed_bgzf  whole BGZF members in file order (the walk, the inflate and the refusals of sg_train_feed_bgzf: a
+ *                     member that is not well formed is SG_ERR_INVALID naming its file offset).  The text goes the way of
+ *                     sg_vcf_feed.  A call that fails delivers nothing: counts, rows and the carried line stay as they were
+ *   sg_vcf_undecided  the undecided fragments of the LAST feed: number, offset into `bytes`, length; valid until the next
+ *                     feed.  SG_ERR_OVERFLOW when `cap` rows or `bytes_cap` bytes do not hold them (*n, *n_bytes say how
+ *                     many there are: call again)
+ *   sg_vcf_finish     the end of the text: a last line without a line break is parsed; the counts.  Rows stay fetchable
+ *   sg_vcf_rows       `n` kept rows of `kind` (SG_VCF_SNV / _INS / _DEL) from row `first` on, in file order
+ *   sg_vcf_end        ends the session and frees its buffers
+ *   sg_vcf_row        host only, no context: the verdict on one fragment (1..19999 bytes), the same code the kernel runs */
+#define SG_VCF_SKIP 0
+#define SG_VCF_SNV 1
+#define SG_VCF_INS 2
+#define SG_VCF_DEL 3
+#define SG_VCF_MALFORMED 4
+#define SG_VCF_UNDECIDED 5
+#define SG_VCF_HOMO 1u    /* flags: the parser files the SNV as homozygous (everything but the genotype "1/1") */
+#define SG_VCF_KNOWN 2u   /* flags: the contig is among the keys (the row is kept) */
+typedef struct sg_vcf_record {
+  uint64_t fragment;   /* its number, from 1: the parser's line_num */
+  int64_t pos;         /* as the parser stores it: POS, POS + 1 of a deletion */
+  uint32_t contig;     /* row among the contig keys */
+  int32_t value;       /* SNV: the first byte of ALT (0: ALT is empty); insertion / deletion: its length */
+  uint32_t kind;       /* SG_VCF_* */
+  uint32_t flags;      /* SG_VCF_HOMO, SG_VCF_KNOWN */
+} sg_vcf_record;
+typedef struct sg_vcf_fragment {
+  uint64_t number;
+  uint64_t offset;     /* where its bytes start */
+  uint32_t len, pad;
+} sg_vcf_fragment;
+typedef struct sg_vcf_counts {
+  uint64_t fragments;                  /* numbered so far */
+  uint64_t n_snv, n_ins, n_del;        /* as the parser counts them: rows on unknown contigs included */
+  uint64_t kept_snv, kept_ins, kept_del;
+  uint64_t malformed;
+  uint64_t malformed_first[11];        /* the numbers of the first eleven */
+  uint64_t undecided;                  /* over all feeds */
+  uint64_t text_bytes;
+} sg_vcf_counts;
+int sg_vcf_begin(sg_ctx* ctx, const char* const* contig_keys, uint32_t n_contigs);
+int sg_vcf_feed(sg_ctx* ctx, const char* text, uint64_t bytes);
+int sg_vcf_feed_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes);
+int sg_vcf_undecided(sg_ctx* ctx, sg_vcf_fragment* rows, uint64_t cap, uint64_t* n, char* bytes, uint64_t bytes_cap, uint64_t* n_bytes);
+int sg_vcf_finish(sg_ctx* ctx, sg_vcf_counts* counts);
+int sg_vcf_rows(sg_ctx* ctx, uint32_t kind, uint64_t first, uint64_t n, sg_vcf_record* rows);
+int sg_vcf_end(sg_ctx* ctx);
+int sg_vcf_row(const char* fragment, uint32_t len, const char* const* contig_keys, uint32_t n_contigs, sg_vcf_record* row);
+
 #ifdef __cplusplus
 }
 #endif

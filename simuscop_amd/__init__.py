@@ -40,6 +40,7 @@ ENGINE_SYMBOLS = [
     "sg_variants_begin", "sg_variants_add", "sg_variants_counts", "sg_variants_reset", "sg_variants_info", "sg_variants_end",
     "sg_variant_observe",
     "sg_errtab_begin", "sg_errtab_add", "sg_errtab_counts", "sg_errtab_reset", "sg_errtab_info", "sg_errtab_end", "sg_errtab_observe",
+    "sg_vcf_begin", "sg_vcf_feed", "sg_vcf_feed_bgzf", "sg_vcf_undecided", "sg_vcf_finish", "sg_vcf_rows", "sg_vcf_end", "sg_vcf_row",
 ]
 
 
@@ -152,6 +153,22 @@ class SgErrtabShape(C.Structure):
     _fields_ = [("cycles", C.c_uint32), ("qual_lo", C.c_uint32), ("n_qual", C.c_uint32), ("tmpl_len", C.c_uint32), ("cells", C.c_uint64),
                 ("bases", C.c_uint64), ("errors", C.c_uint64), ("skipped", C.c_uint64), ("reads", C.c_uint64),
                 ("win_cycles", C.c_uint32), ("lds_bytes", C.c_uint32)]
+
+
+class SgVcfRecord(C.Structure):
+    """sg_vcf_record (include/simuscop_amd.h): one fragment's verdict"""
+    _fields_ = [("fragment", C.c_uint64), ("pos", C.c_int64), ("contig", C.c_uint32), ("value", C.c_int32), ("kind", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class SgVcfFragment(C.Structure):
+    _fields_ = [("number", C.c_uint64), ("offset", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SgVcfCounts(C.Structure):
+    _fields_ = [("fragments", C.c_uint64), ("n_snv", C.c_uint64), ("n_ins", C.c_uint64), ("n_del", C.c_uint64), ("kept_snv", C.c_uint64),
+                ("kept_ins", C.c_uint64), ("kept_del", C.c_uint64), ("malformed", C.c_uint64), ("malformed_first", C.c_uint64 * 11),
+                ("undecided", C.c_uint64), ("text_bytes", C.c_uint64)]
 
 
 class SgHapPatch(C.Structure):
@@ -335,6 +352,14 @@ def load_engine():
     lib.sg_errtab_end.argtypes = [vp]
     lib.sg_errtab_observe.argtypes = [u8p, C.c_uint32, C.c_int, u32p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.c_uint32, u64p, C.c_uint64]
+    lib.sg_vcf_begin.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint32]
+    lib.sg_vcf_feed.argtypes = [vp, C.c_char_p, C.c_uint64]
+    lib.sg_vcf_feed_bgzf.argtypes = [vp, C.c_char_p, C.c_uint64]
+    lib.sg_vcf_undecided.argtypes = [vp, C.POINTER(SgVcfFragment), C.c_uint64, u64p, C.c_char_p, C.c_uint64, u64p]
+    lib.sg_vcf_finish.argtypes = [vp, C.POINTER(SgVcfCounts)]
+    lib.sg_vcf_rows.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SgVcfRecord)]
+    lib.sg_vcf_end.argtypes = [vp]
+    lib.sg_vcf_row.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(SgVcfRecord)]
     _engine = lib
     return lib
 
@@ -424,7 +449,7 @@ class SimuTrainOptions(C.Structure):
     _fields_ = [("bam", C.c_char_p), ("sam", C.c_char_p), ("target", C.c_char_p), ("vcf", C.c_char_p), ("ref", C.c_char_p),
                 ("output", C.c_char_p), ("samtools", C.c_char_p), ("kmer", C.c_int32), ("bins", C.c_int32), ("device", C.c_int32),
                 ("threads", C.c_int32), ("quiet", C.c_int32), ("stamp", C.c_char_p), ("max_reads", C.c_uint64),
-                ("decode_bam", C.c_int32)]
+                ("decode_bam", C.c_int32), ("device_vcf", C.c_int32)]
 
 
 class SimuTrainStats(C.Structure):
@@ -432,13 +457,17 @@ class SimuTrainStats(C.Structure):
                 ("gc_pairs", C.c_uint64), ("skipped_overhang", C.c_uint64), ("sam_bytes", C.c_uint64), ("read_length", C.c_int32),
                 ("bins", C.c_int32), ("gc_fitted", C.c_int32), ("capped", C.c_int32), ("t_reference", C.c_double), ("t_reads", C.c_double), ("t_total", C.c_double),
                 ("insert_rate", C.c_double), ("del_rate", C.c_double), ("std_isize", C.c_double), ("gc_std", C.c_double),
-                ("bam_bytes", C.c_uint64), ("bam_records", C.c_uint64), ("t_inflate", C.c_double)]
+                ("bam_bytes", C.c_uint64), ("bam_records", C.c_uint64), ("t_inflate", C.c_double),
+                ("t_vcf", C.c_double), ("vcf_bytes", C.c_uint64), ("vcf_fragments", C.c_uint64), ("vcf_undecided", C.c_uint64),
+                ("vcf_on_device", C.c_int32)]
 
 
 def train_profile(ref: str, vcf: str, output: str, sam: str = "", bam: str = "", target: str = "", samtools: str = "", kmer: int = 3,
-                  bins: int = 50, device: int = 0, quiet: int = 1, stamp: str = None, max_reads: int = 0, decode_bam: bool = False) -> SimuTrainStats:
+                  bins: int = 50, device: int = 0, quiet: int = 1, stamp: str = None, max_reads: int = 0, decode_bam: bool = False,
+                  device_vcf: bool = False) -> SimuTrainStats:
     """`seqToProfile` in-process (src/seqToProfile.cpp main): reads (`sam`: a file of `samtools view` text, or `bam` through
-    samtools as the reference does), the sample's VCF and the reference -> a .profile file; the per-read work runs on the GPU."""
+    samtools as the reference does), the sample's VCF and the reference -> a .profile file; the per-read work runs on the GPU.
+    A bgzip-compressed `vcf` is inflated and parsed on the GPU; `device_vcf` sends a plain-text one the same way."""
     lib = load_host()
     lib.simu_train_default_options.argtypes = [C.POINTER(SimuTrainOptions)]
     lib.simu_train_default_options.restype = None
@@ -448,6 +477,7 @@ def train_profile(ref: str, vcf: str, output: str, sam: str = "", bam: str = "",
     o.bam, o.sam, o.target, o.vcf, o.ref, o.output, o.samtools = (x.encode() for x in (bam, sam, target, vcf, ref, output, samtools))
     o.kmer, o.bins, o.device, o.quiet, o.max_reads = kmer, bins, device, quiet, max_reads
     o.decode_bam = 1 if decode_bam else 0
+    o.device_vcf = 1 if device_vcf else 0
     if stamp is not None:
         o.stamp = stamp.encode()
     st = SimuTrainStats()
@@ -683,6 +713,79 @@ def deflate_bgzf(ctx, text: bytes) -> bytes:
     out, n = C.create_string_buffer(cap), C.c_uint64()
     _bamindex_check(eng, ctx, eng.sg_deflate_bgzf(ctx, text, len(text), out, cap, C.byref(n)), "sg_deflate_bgzf")
     return out.raw[:n.value]
+
+
+VCF_KINDS = ("skip", "snv", "ins", "del", "malformed", "undecided")   # SG_VCF_*
+VCF_HOMO, VCF_KNOWN = 1, 2
+
+
+def _vcf_check(eng, ctx, rc, who):
+    if rc != 0:
+        raise SimuError(f"{who} failed ({rc}): {eng.sg_last_error(ctx).decode(errors='replace')}")
+
+
+def _vcf_keys(keys):
+    keys = [k if isinstance(k, bytes) else k.encode() for k in keys]
+    return (C.c_char_p * max(len(keys), 1))(*keys), len(keys)
+
+
+def vcf_row(fragment: bytes, keys):
+    """sg_vcf_row (host only, no GPU): the verdict on one fragment of at most 19,999 bytes.  Returns (kind, pos, contig, value,
+    flags) with kind one of VCF_KINDS."""
+    lib = load_engine()
+    arr, n = _vcf_keys(keys)
+    r = SgVcfRecord()
+    rc = lib.sg_vcf_row(fragment, len(fragment), arr, n, C.byref(r))
+    if rc != 0:
+        raise SimuError(f"sg_vcf_row failed ({rc})")
+    return VCF_KINDS[r.kind], r.pos, r.contig, r.value, r.flags
+
+
+def vcf_begin(ctx, keys) -> None:
+    """sg_vcf_begin on a bare engine context `ctx` (sg_create)."""
+    eng = load_engine()
+    arr, n = _vcf_keys(keys)
+    _vcf_check(eng, ctx, eng.sg_vcf_begin(ctx, arr, n), "sg_vcf_begin")
+
+
+def vcf_undecided(ctx):
+    """sg_vcf_undecided: [(fragment number, bytes)] of the last feed."""
+    eng = load_engine()
+    n, nb = C.c_uint64(), C.c_uint64()
+    rc = eng.sg_vcf_undecided(ctx, None, 0, C.byref(n), None, 0, C.byref(nb))
+    if rc == 0 and n.value == 0:
+        return []
+    rows, buf = (SgVcfFragment * n.value)(), C.create_string_buffer(max(nb.value, 1))
+    _vcf_check(eng, ctx, eng.sg_vcf_undecided(ctx, rows, n.value, C.byref(n), buf, nb.value, C.byref(nb)), "sg_vcf_undecided")
+    return [(r.number, buf.raw[r.offset:r.offset + r.len]) for r in rows]
+
+
+def vcf_feed(ctx, text: bytes, bgzf: bool = False):
+    """sg_vcf_feed / sg_vcf_feed_bgzf; returns the feed's undecided fragments (vcf_undecided)."""
+    eng = load_engine()
+    call, who = (eng.sg_vcf_feed_bgzf, "sg_vcf_feed_bgzf") if bgzf else (eng.sg_vcf_feed, "sg_vcf_feed")
+    _vcf_check(eng, ctx, call(ctx, text, len(text)), who)
+    return vcf_undecided(ctx)
+
+
+def vcf_finish(ctx):
+    """sg_vcf_finish -> (SgVcfCounts, the undecided fragments of the flushed last line)"""
+    eng = load_engine()
+    c = SgVcfCounts()
+    _vcf_check(eng, ctx, eng.sg_vcf_finish(ctx, C.byref(c)), "sg_vcf_finish")
+    return c, vcf_undecided(ctx)
+
+
+def vcf_rows(ctx, kind: str, n: int, first: int = 0):
+    """sg_vcf_rows: kept rows of `kind` ("snv", "ins", "del") as (fragment, pos, contig, value, flags) tuples"""
+    eng = load_engine()
+    rows = (SgVcfRecord * max(n, 1))()
+    _vcf_check(eng, ctx, eng.sg_vcf_rows(ctx, VCF_KINDS.index(kind), first, n, rows), "sg_vcf_rows")
+    return [(r.fragment, r.pos, r.contig, r.value, r.flags) for r in rows[:n]]
+
+
+def vcf_end(ctx) -> None:
+    load_engine().sg_vcf_end(ctx)
 
 
 def bai_build(ref_len, rows, linear, counts):

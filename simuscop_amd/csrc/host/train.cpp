@@ -58,7 +58,56 @@ struct KnownVariants {
   std::vector<int32_t> ins_len, del_len;
   uint64_t n_snv = 0, n_ins = 0, n_del = 0;   // as the reference counts them (rows on contigs the FASTA lacks included)
 };
-void parse_vcf(const std::string& path, const std::map<std::string, uint32_t>& row_of, KnownVariants& kv, bool quiet) {
+// What the parser's loop does with one fragment -- what one fgets(buf, 20000) returned, NUL terminated; the fields are cut in
+// place.  False: malformed (fewer than ten fields).  Both VCF routes run this: the host route on every fragment, the device
+// route on those the device hands back undecided (csrc/sg_vcf.h).
+bool vcf_fragment(char* buf, const std::map<std::string, uint32_t>& row_of, KnownVariants& kv) {
+  if (buf[0] == '#') return true;
+  // ten fields, the rest of the line stays with the tenth
+  char* f[10];
+  int nf = 0;
+  char* p = buf;
+  f[nf++] = p;
+  while (*p && nf < 10) {
+    if (*p == '\t') { *p = '\0'; f[nf++] = p + 1; }
+    p++;
+  }
+  if (nf < 10) return false;
+  const std::string info = f[7];
+  const size_t dp = info.find("DP=");
+  if (dp != std::string::npos) {
+    const size_t semi = info.find(";", dp);
+    if (atoi(info.substr(dp + 3, semi - dp - 3).c_str()) < 10) return true;   // depth_th
+  }
+  if ((float)atof(f[5]) < 20.0f) return true;                                  // quality_th
+  const std::string chr = abbr_of_chr(f[0]);
+  const long pos = atol(f[1]);
+  std::string gt = f[9];
+  gt = gt.substr(0, gt.find(':'));
+  // (the parser files 1/1 as het and everything else as homo, :81-86: kept as it is -- including what fgets leaves behind:
+  // a sample column that holds the genotype alone ends in the line break, and "1/1\n" is not "1/1")
+  const bool homo = gt != "1/1";
+  const auto it = row_of.find(chr);
+  const size_t ref_len = strlen(f[3]), alt_len = strlen(f[4]);
+  if (ref_len > 1) {
+    kv.n_del++;
+    if (it != row_of.end()) { kv.del_contig.push_back(it->second); kv.del_pos.push_back(pos + 1); kv.del_len.push_back((int32_t)ref_len - 1); }
+  } else if (alt_len > 1) {
+    kv.n_ins++;
+    if (it != row_of.end()) { kv.ins_contig.push_back(it->second); kv.ins_pos.push_back(pos); kv.ins_len.push_back((int32_t)alt_len - 1); }
+  } else {
+    kv.n_snv++;
+    if (it != row_of.end()) { kv.snv_contig.push_back(it->second); kv.snv_pos.push_back(pos); kv.snv_alt.push_back(f[4][0]); kv.snv_homo.push_back(homo ? 1 : 0); }
+  }
+  return true;
+}
+void vcf_malformed_warning(const std::string& path, uint64_t line_num) {
+  std::cerr << "Warning: malformed VCF file " << path << ", there should be at least 10 fields @line " << line_num << std::endl;
+}
+void vcf_total_line(const std::string& path, const KnownVariants& kv) {
+  std::cerr << "total " << kv.n_snv << " SNPs, " << kv.n_ins << " inserts and " << kv.n_del << " deletions were loaded from file " << path << std::endl;
+}
+void parse_vcf(const std::string& path, const std::map<std::string, uint32_t>& row_of, KnownVariants& kv, bool quiet, simu_train_stats& st) {
   if (path.empty()) { std::cerr << "Error: VCF file was not specified" << std::endl; return; }
   FILE* fp = fopen(path.c_str(), "r");
   if (!fp) throw Error("Error: cannot open VCF file " + path, -1);
@@ -67,51 +116,31 @@ void parse_vcf(const std::string& path, const std::map<std::string, uint32_t>& r
   int wrong = 0;
   while (fgets(buf.data(), (int)buf.size(), fp)) {
     line_num++;
-    if (buf[0] == '#') continue;
-    // ten fields, the rest of the line stays with the tenth
-    char* f[10];
-    int nf = 0;
-    char* p = buf.data();
-    f[nf++] = p;
-    while (*p && nf < 10) {
-      if (*p == '\t') { *p = '\0'; f[nf++] = p + 1; }
-      p++;
-    }
-    if (nf < 10) {
-      std::cerr << "Warning: malformed VCF file " << path << ", there should be at least 10 fields @line " << line_num << std::endl;
+    if (!vcf_fragment(buf.data(), row_of, kv)) {
+      vcf_malformed_warning(path, (uint64_t)line_num);
       if (++wrong > 10) { fclose(fp); throw Error("", 1); }
-      continue;
-    }
-    const std::string info = f[7];
-    const size_t dp = info.find("DP=");
-    if (dp != std::string::npos) {
-      const size_t semi = info.find(";", dp);
-      if (atoi(info.substr(dp + 3, semi - dp - 3).c_str()) < 10) continue;   // depth_th
-    }
-    if ((float)atof(f[5]) < 20.0f) continue;                                  // quality_th
-    const std::string chr = abbr_of_chr(f[0]);
-    const long pos = atol(f[1]);
-    std::string gt = f[9];
-    gt = gt.substr(0, gt.find(':'));
-    // (the parser files 1/1 as het and everything else as homo, :81-86: kept as it is -- including what fgets leaves behind:
-    // a sample column that holds the genotype alone ends in the line break, and "1/1\n" is not "1/1")
-    const bool homo = gt != "1/1";
-    const auto it = row_of.find(chr);
-    const size_t ref_len = strlen(f[3]), alt_len = strlen(f[4]);
-    if (ref_len > 1) {
-      kv.n_del++;
-      if (it != row_of.end()) { kv.del_contig.push_back(it->second); kv.del_pos.push_back(pos + 1); kv.del_len.push_back((int32_t)ref_len - 1); }
-    } else if (alt_len > 1) {
-      kv.n_ins++;
-      if (it != row_of.end()) { kv.ins_contig.push_back(it->second); kv.ins_pos.push_back(pos); kv.ins_len.push_back((int32_t)alt_len - 1); }
-    } else {
-      kv.n_snv++;
-      if (it != row_of.end()) { kv.snv_contig.push_back(it->second); kv.snv_pos.push_back(pos); kv.snv_alt.push_back(f[4][0]); kv.snv_homo.push_back(homo ? 1 : 0); }
     }
   }
+  const long at = ftell(fp);
+  st.vcf_bytes = at > 0 ? (uint64_t)at : 0;
+  st.vcf_fragments = (uint64_t)line_num;
   fclose(fp);
-  if (!quiet)
-    std::cerr << "total " << kv.n_snv << " SNPs, " << kv.n_ins << " inserts and " << kv.n_del << " deletions were loaded from file " << path << std::endl;
+  if (!quiet) vcf_total_line(path, kv);
+}
+
+// ---- the VCF through the device (sg_vcf_*, csrc/sg_vcf.h): the same rows, warnings and counts ----
+enum class VcfForm { Plain, Bgzf, Gzip };
+// What the file's first bytes say: gzip magic with a well-formed BGZF member header (SAMv1 section 4.1), gzip without, or
+// anything else.  A file that cannot be opened is Plain: parse_vcf reports it where it always did.
+VcfForm vcf_form(const std::string& path) {
+  FILE* fp = path.empty() ? nullptr : fopen(path.c_str(), "rb");
+  if (!fp) return VcfForm::Plain;
+  std::vector<uint8_t> head(65536 + 64);
+  const size_t n = fread(head.data(), 1, head.size(), fp);
+  fclose(fp);
+  if (n < 2 || head[0] != 31 || head[1] != 139) return VcfForm::Plain;
+  uint64_t n_members = 0, whole = 0;
+  return sg_bgzf_members(head.data(), n, nullptr, nullptr, nullptr, 1, &n_members, &whole) == SG_OK ? VcfForm::Bgzf : VcfForm::Gzip;
 }
 
 // ---- Genome::loadTargets (Genome.cpp:238-299) + divideTargets (:684-739) into inTargets ----
@@ -207,6 +236,7 @@ struct ChunkReader {
   uint64_t len[2] = {0, 0};
   std::string carry;          // the unfinished line behind a chunk's last line break
   bool eof = false;
+  bool whole_lines = true;    // false: chunks are cut wherever they end (the VCF route: the device carries the partial line)
   ChunkReader(sg_ctx* c, FILE* f, int threads) : ctx(c), fp(f) {
     struct stat sb;
     if (f != stdin && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
@@ -241,7 +271,7 @@ struct ChunkReader {
         have += got;
       }
     }
-    if (!eof) {   // cut behind the last line break
+    if (!eof && whole_lines) {   // cut behind the last line break
       uint64_t cut = have;
       while (cut > 0 && buf[i][cut - 1] != '\n') cut--;
       if (cut == 0) throw Error("a line of the SAM text is longer than 64 MB");
@@ -255,15 +285,18 @@ struct ChunkReader {
 
 // ---- --decode-bam: the BAM file itself, read in batches of whole BGZF members (SAMv1 section 4.1) ----
 constexpr uint64_t kBamBatch = 16ull << 20;   // compressed bytes per batch (about 3 to 4 times as many inflated)
+constexpr uint64_t kVcfBatch = 8ull << 20;    // of a BGZF VCF (text: several times more per byte than BAM records)
 constexpr uint32_t kMaxMember = 65536;        // BSIZE is 16 bits
 
 uint32_t le32(const uint8_t* p) { return p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 // Pinned batches cut at a member boundary, read ahead while the device works on the batch before: a regular file by the pread
-// pool, standard input by fread.  A member cut by the end of the file is an error.
+// pool, standard input by fread.  A member cut by the end of the file is an error.  Any BGZF file: the BAM of --decode-bam,
+// a bgzip-compressed VCF (`kind` names it in the open error, `batch` is the compressed bytes of a batch).
 struct BamReader {
   sg_ctx* ctx;
   std::string what;
+  uint64_t batch = kBamBatch;
   FILE* fp = nullptr;
   int fd = -1;
   uint64_t pos = 0, size = 0, file_off = 0;   // file_off: where the next batch starts
@@ -273,9 +306,10 @@ struct BamReader {
   std::string pending;   // bytes behind the last whole member of a batch
   std::string last28;    // the last 28 bytes read (the EOF member, if the file has one)
   bool eof = false;
-  BamReader(sg_ctx* c, const std::string& path, int threads) : ctx(c), what(path) {
+  BamReader(sg_ctx* c, const std::string& path, int threads, const char* kind = "BAM", uint64_t batch_bytes = kBamBatch)
+      : ctx(c), what(path), batch(batch_bytes) {
     if (path == "-") fp = stdin;
-    else if (!(fp = fopen(path.c_str(), "rb"))) throw Error("cannot open BAM file " + path, -1);
+    else if (!(fp = fopen(path.c_str(), "rb"))) throw Error(std::string("cannot open ") + kind + " file " + path, -1);
     struct stat sb;
     if (fp != stdin && fstat(fileno(fp), &sb) == 0 && S_ISREG(sb.st_mode)) {
       fd = fileno(fp);
@@ -284,7 +318,7 @@ struct BamReader {
     }
     for (int i = 0; i < 2; i++) {
       void* p = nullptr;
-      if (sg_host_alloc(ctx, kBamBatch + kMaxMember, &p) != SG_OK) throw Error(std::string("GPU engine error in sg_host_alloc: ") + sg_last_error(ctx));
+      if (sg_host_alloc(ctx, batch + kMaxMember, &p) != SG_OK) throw Error(std::string("GPU engine error in sg_host_alloc: ") + sg_last_error(ctx));
       buf[i] = (char*)p;
     }
   }
@@ -306,14 +340,14 @@ struct BamReader {
     memcpy(buf[i], pending.data(), have);
     pending.clear();
     if (fd >= 0) {
-      const uint64_t n = std::min<uint64_t>(kBamBatch + kMaxMember - have, size - pos);
+      const uint64_t n = std::min<uint64_t>(batch + kMaxMember - have, size - pos);
       if (n) parallel_pread(*pool, fd, (uint8_t*)buf[i] + have, pos, n);
       have += n;
       pos += n;
       if (pos >= size) eof = true;
     } else {
-      while (!eof && have < kBamBatch + kMaxMember) {
-        const size_t got = fread(buf[i] + have, 1, kBamBatch + kMaxMember - have, fp);
+      while (!eof && have < batch + kMaxMember) {
+        const size_t got = fread(buf[i] + have, 1, batch + kMaxMember - have, fp);
         if (got == 0) { eof = true; break; }
         have += got;
       }
@@ -428,6 +462,122 @@ void bam_prepare(sg_ctx* ctx, BamReader& rd, BamHeader& H, int& read_length, std
     dec_off += p;
   }
   if (!have_header) throw Error("Error: truncated BAM header in " + rd.what);
+}
+
+// The device route of the VCF: the file's text (plain: pinned chunks cut anywhere; BGZF: batches of whole members) goes
+// through sg_vcf_feed / sg_vcf_feed_bgzf while a reader thread fills the next chunk.  The fragments the device leaves
+// undecided go through vcf_fragment here and are merged back by fragment number, so every list keeps the file's order.
+void load_vcf_device(sg_ctx* ctx, const std::string& path, bool bgzf, const std::map<std::string, uint32_t>& row_of, KnownVariants& kv, bool quiet, int threads, simu_train_stats& st) {
+  auto said = [&](int rc, const char* where) {
+    if (rc == SG_OK) return;
+    const std::string m = sg_last_error(ctx);
+    if (rc == SG_ERR_INVALID) throw Error("Error: " + m + " (" + path + ")", 1);
+    throw Error(std::string("GPU engine error in ") + where + ": " + m);
+  };
+  std::vector<const char*> keys;      // the map's keys, and the row each one stands for
+  std::vector<uint32_t> row_of_key;
+  for (const auto& kr : row_of) { keys.push_back(kr.first.c_str()); row_of_key.push_back(kr.second); }
+  said(sg_vcf_begin(ctx, keys.data(), (uint32_t)keys.size()), "sg_vcf_begin");
+  struct Session { sg_ctx* c; ~Session() { sg_vcf_end(c); } } session{ctx};
+  KnownVariants hv;                                    // what the host resolved, and the fragment numbers of its kept rows
+  std::vector<uint64_t> h_num[3], h_malformed;
+  std::vector<char> buf(20000);
+  auto resolve = [&]() {
+    uint64_t n = 0, nb = 0;
+    const int rc = sg_vcf_undecided(ctx, nullptr, 0, &n, nullptr, 0, &nb);
+    if (rc == SG_OK && !n) return;
+    if (rc != SG_ERR_OVERFLOW) said(rc, "sg_vcf_undecided");
+    std::vector<sg_vcf_fragment> fr(n);
+    std::vector<char> bytes(nb + 1);
+    said(sg_vcf_undecided(ctx, fr.data(), n, &n, bytes.data(), nb, &nb), "sg_vcf_undecided");
+    for (const sg_vcf_fragment& f : fr) {
+      memcpy(buf.data(), bytes.data() + f.offset, f.len);
+      buf[f.len] = '\0';
+      const size_t before[3] = {hv.snv_pos.size(), hv.ins_pos.size(), hv.del_pos.size()};
+      if (!vcf_fragment(buf.data(), row_of, hv)) h_malformed.push_back(f.number);
+      if (hv.snv_pos.size() > before[0]) h_num[0].push_back(f.number);
+      if (hv.ins_pos.size() > before[1]) h_num[1].push_back(f.number);
+      if (hv.del_pos.size() > before[2]) h_num[2].push_back(f.number);
+    }
+  };
+  if (bgzf) {
+    BamReader rd(ctx, path, threads, "VCF", kVcfBatch);
+    if (rd.fd >= 0) {
+      if (rd.size >= 28) {
+        rd.last28.resize(28);
+        if (pread(rd.fd, &rd.last28[0], 28, (off_t)(rd.size - 28)) != 28) rd.last28.clear();
+      }
+      if (!rd.eof_marker()) std::cerr << "Warning: no BGZF EOF marker at the end of " << path << ". The input is probably truncated" << std::endl;
+    }
+    int cur = 0;
+    bool more = rd.fill(cur);
+    while (more) {
+      bool next = false;
+      std::string reader_error;
+      std::thread reader([&]() { try { next = rd.fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
+      const int rc = sg_vcf_feed_bgzf(ctx, rd.buf[cur], rd.len[cur]);
+      reader.join();
+      said(rc, "sg_vcf_feed_bgzf");
+      if (!reader_error.empty()) throw Error(reader_error);
+      resolve();
+      cur ^= 1;
+      more = next;
+    }
+  } else {
+    FILE* fp = fopen(path.c_str(), "rb");
+    if (!fp) throw Error("Error: cannot open VCF file " + path, -1);
+    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    ChunkReader rd(ctx, fp, threads);
+    rd.whole_lines = false;
+    int cur = 0;
+    bool more = rd.fill(cur);
+    while (more) {
+      bool next = false;
+      std::string reader_error;
+      std::thread reader([&]() { try { next = rd.fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
+      const int rc = sg_vcf_feed(ctx, rd.buf[cur], rd.len[cur]);
+      reader.join();
+      said(rc, "sg_vcf_feed");
+      if (!reader_error.empty()) throw Error(reader_error);
+      resolve();
+      cur ^= 1;
+      more = next;
+    }
+  }
+  sg_vcf_counts C;
+  said(sg_vcf_finish(ctx, &C), "sg_vcf_finish");
+  resolve();   // (a last line without a line break)
+  // ---- the warnings of malformed fragments, in file order; more than ten end the run (vcfparser.cpp:44-51) ----
+  std::vector<uint64_t> bad(C.malformed_first, C.malformed_first + std::min<uint64_t>(C.malformed, 11));
+  bad.insert(bad.end(), h_malformed.begin(), h_malformed.end());
+  std::sort(bad.begin(), bad.end());
+  const uint64_t n_bad = C.malformed + h_malformed.size();
+  for (size_t i = 0; i < bad.size() && i < 11; i++) vcf_malformed_warning(path, bad[i]);
+  if (n_bad > 10) throw Error("", 1);
+  // ---- the rows: the device's and the host's, by fragment number ----
+  const uint64_t n_dev[3] = {C.kept_snv, C.kept_ins, C.kept_del};
+  for (int k = 0; k < 3; k++) {
+    std::vector<sg_vcf_record> rows(n_dev[k]);
+    said(sg_vcf_rows(ctx, (uint32_t)(SG_VCF_SNV + k), 0, n_dev[k], rows.data()), "sg_vcf_rows");
+    size_t d = 0, h = 0;
+    while (d < rows.size() || h < h_num[k].size()) {
+      const bool from_host = d == rows.size() || (h < h_num[k].size() && h_num[k][h] < rows[d].fragment);
+      if (k == 0) {
+        if (from_host) { kv.snv_contig.push_back(hv.snv_contig[h]); kv.snv_pos.push_back(hv.snv_pos[h]); kv.snv_alt.push_back(hv.snv_alt[h]); kv.snv_homo.push_back(hv.snv_homo[h]); }
+        else { kv.snv_contig.push_back(row_of_key[rows[d].contig]); kv.snv_pos.push_back(rows[d].pos); kv.snv_alt.push_back((char)rows[d].value); kv.snv_homo.push_back((rows[d].flags & SG_VCF_HOMO) ? 1 : 0); }
+      } else {
+        std::vector<uint32_t>& contig = k == 1 ? kv.ins_contig : kv.del_contig;
+        std::vector<int64_t>& pos = k == 1 ? kv.ins_pos : kv.del_pos;
+        std::vector<int32_t>& len = k == 1 ? kv.ins_len : kv.del_len;
+        if (from_host) { contig.push_back((k == 1 ? hv.ins_contig : hv.del_contig)[h]); pos.push_back((k == 1 ? hv.ins_pos : hv.del_pos)[h]); len.push_back((k == 1 ? hv.ins_len : hv.del_len)[h]); }
+        else { contig.push_back(row_of_key[rows[d].contig]); pos.push_back(rows[d].pos); len.push_back(rows[d].value); }
+      }
+      if (from_host) h++; else d++;
+    }
+  }
+  kv.n_snv = C.n_snv + hv.n_snv; kv.n_ins = C.n_ins + hv.n_ins; kv.n_del = C.n_del + hv.n_del;
+  st.vcf_bytes = C.text_bytes; st.vcf_fragments = C.fragments; st.vcf_undecided = C.undecided; st.vcf_on_device = 1;
+  if (!quiet) vcf_total_line(path, kv);
 }
 
 // ---- the arithmetic of Profile::train behind the counting (Profile.cpp:1471-1483) ----
@@ -642,6 +792,10 @@ void run(const simu_train_options& o, simu_train_stats& st) {
   const auto t0 = Clock::now();
   const bool quiet = o.quiet != 0;
   const std::string ref = o.ref ? o.ref : "", vcf = o.vcf ? o.vcf : "", target = o.target ? o.target : "", output = o.output ? o.output : "";
+  // a compressed VCF: BGZF goes through the device, any other gzip file is refused before anything is touched
+  const VcfForm form = vcf_form(vcf);
+  if (form == VcfForm::Gzip)
+    throw Error("Error: VCF file " + vcf + " is gzip-compressed but not BGZF: decompress it, or recompress it with bgzip", 1);
   Engine eng;
   if (sg_create(&eng.ctx, o.device, 0) != SG_OK) throw Error(std::string("GPU engine error: ") + sg_last_error(nullptr));
   // ---- Genome::loadTrainData: VCF, reference, targets (Genome.cpp:32-39; the VCF needs the contig rows, so the reference
@@ -655,7 +809,12 @@ void run(const simu_train_options& o, simu_train_stats& st) {
   std::vector<std::string> key_of_row(fa.contigs.size());
   for (const auto& kv : fa.contig_of) key_of_row[kv.second] = kv.first;
   KnownVariants kv;
-  parse_vcf(vcf, fa.contig_of, kv, quiet);
+  t1 = Clock::now();
+  if (form == VcfForm::Bgzf || (o.device_vcf && !vcf.empty()))
+    load_vcf_device(eng.ctx, vcf, form == VcfForm::Bgzf, fa.contig_of, kv, quiet, std::max(1, o.threads), st);
+  else
+    parse_vcf(vcf, fa.contig_of, kv, quiet, st);
+  st.t_vcf = since(t1);
   const std::map<std::string, std::vector<Piece>> targets = load_targets(target, fa, quiet);
   std::vector<uint64_t> tfirst(key_of_row.size() + 1, 0);
   std::vector<int64_t> tspos, tepos;

@@ -27,6 +27,8 @@ typedef struct simu_train_options {
                           // (600,000,000 with targets), behind which it stops reading (Profile.cpp:236, 497-507)
   int32_t decode_bam;     // --decode-bam (additive): `bam` is read and decoded here (BGZF inflate and the records on the GPU) instead
                           // of through samtools; the lines are the ones `samtools view -F 0xD04 -q 20` prints
+  int32_t device_vcf;     // --device-vcf (additive): a plain-text `vcf` is parsed on the GPU (sg_vcf_feed) instead of by the host's
+                          // fgets loop; same rows, warnings and exit codes.  A BGZF `vcf` (x.vcf.gz as bgzip writes it) always is
 } simu_train_options;
 
 typedef struct simu_train_stats {
@@ -36,6 +38,9 @@ typedef struct simu_train_stats {
   double insert_rate, del_rate, std_isize, gc_std;
   uint64_t bam_bytes, bam_records;   // --decode-bam: BGZF bytes fed, records decoded (kept or not)
   double t_inflate;                  // seconds in sg_train_feed_bgzf (inflate, record boundaries, rendering)
+  double t_vcf;                      // seconds reading the VCF, on either route
+  uint64_t vcf_bytes, vcf_fragments, vcf_undecided;   // its text; what fgets(buf, 20000) would return; those the device handed back
+  int32_t vcf_on_device;             // 1: the device route (a BGZF file, or --device-vcf)
 } simu_train_stats;
 
 void simu_train_default_options(simu_train_options* o);

@@ -4,6 +4,8 @@
 //   --sam <file|->   lines of `samtools view -F 0xD04 -q 20` text from a file or standard input (instead of running samtools)
 //   --decode-bam     with -b: the BAM file is read here -- BGZF inflated and the records decoded on the GPU -- instead of through
 //                    `samtools view -F 0xD04 -q 20` (same lines, no samtools needed; -s is ignored)
+//   --device-vcf     a plain-text -v file is parsed on the GPU instead of by the host's fgets loop (same rows, warnings and
+//                    exit codes).  A bgzip-compressed -v file (x.vcf.gz, BGZF) always is: inflated and parsed on the GPU
 //   --max-reads <n>  Profile::processRead's cap on counted reads (default: the reference's 300,000,000; twice that with targets)
 //   --device <n>     GPU to use (default 0)        --quiet   no progress lines        --stats   one JSON line of counts and times
 #include <getopt.h>
@@ -30,13 +32,15 @@ static void usage(const char* app) {
             << "    -B, --bins <int>                the number of bins into which bases of read are grouped [default:50]\n"
             << "        --sam <file|->              (GPU build) reads as `samtools view` text from a file or standard input\n"
             << "        --decode-bam                (GPU build) with -b: decode the BAM file on the GPU instead of running samtools\n"
+            << "        --device-vcf                (GPU build) parse a plain-text VCF on the GPU (a bgzip-compressed one always is)\n"
             << "        --device <int>              (GPU build) device to use [default:0]\n"
             << "        --quiet                     (GPU build) no progress lines\n"
             << "        --max-reads <int>           (GPU build) stop at so many counted reads [default: the reference's 300000000,\n"
             << "                                    twice that with targets]\n\n"
             << "Example:\n"
             << "    " << app << " -b normal.bam -v normal.vcf -r ref.fa -o results.model -s /path/to/samtools\n"
-            << "    samtools view -F 0xD04 -q 20 normal.bam | " << app << " --sam - -v normal.vcf -r ref.fa > results.model\n\n";
+            << "    samtools view -F 0xD04 -q 20 normal.bam | " << app << " --sam - -v normal.vcf -r ref.fa > results.model\n"
+            << "    " << app << " -b normal.bam --decode-bam -v normal.vcf.gz -r ref.fa -o results.model\n\n";
 }
 
 int main(int argc, char* argv[]) {
@@ -49,7 +53,7 @@ int main(int argc, char* argv[]) {
       {"vcf", required_argument, 0, 'v'},   {"ref", required_argument, 0, 'r'},    {"output", required_argument, 0, 'o'},
       {"samtools", required_argument, 0, 's'}, {"kmer", required_argument, 0, 'k'}, {"bins", required_argument, 0, 'B'},
       {"sam", required_argument, 0, 1000},  {"device", required_argument, 0, 1001}, {"quiet", no_argument, 0, 1002},   {"stats", no_argument, 0, 1003},      {"max-reads", required_argument, 0, 1004},
-      {"decode-bam", no_argument, 0, 1005},
+      {"decode-bam", no_argument, 0, 1005}, {"device-vcf", no_argument, 0, 1006},
       {0, 0, 0, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "hb:t:v:r:o:s:k:B:", long_options, NULL)) != -1) {
@@ -69,6 +73,7 @@ int main(int argc, char* argv[]) {
       case 1003: stats = true; break;
       case 1004: o.max_reads = strtoull(optarg, nullptr, 10); break;
       case 1005: o.decode_bam = 1; break;
+      case 1006: o.device_vcf = 1; break;
       default: usage(argv[0]); return 1;
     }
   }
@@ -125,6 +130,9 @@ int main(int argc, char* argv[]) {
     if (o.decode_bam)   // BGZF bytes fed, records decoded (kept or not), seconds of the decode stage
       fprintf(stderr, ", \"bam_bytes\": %llu, \"bam_records\": %llu, \"t_inflate\": %.4f", (unsigned long long)st.bam_bytes,
               (unsigned long long)st.bam_records, st.t_inflate);
+    // the VCF: seconds, bytes of text, fragments (what fgets(buf, 20000) returns), those the device handed back, the route
+    fprintf(stderr, ", \"t_vcf\": %.4f, \"vcf_bytes\": %llu, \"vcf_fragments\": %llu, \"vcf_undecided\": %llu, \"vcf_on_device\": %d", st.t_vcf,
+            (unsigned long long)st.vcf_bytes, (unsigned long long)st.vcf_fragments, (unsigned long long)st.vcf_undecided, st.vcf_on_device);
     fprintf(stderr, "}\n");
   }
   if (!o.quiet) {

@@ -7,7 +7,8 @@
 //   sg_api_truth.cpp       truth alignments and the truth BAM: sg_pass_prelude, sg_truth_*, sg_pass_records, sg_fetch_truth
 //   sg_api_haplotypes.cpp  reference ingest and haplotype assembly: sg_reference_*, sg_build / upload_haplotypes, sg_haplotype_codes
 //   sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM input), sg_api_depth.cpp / _variants.cpp /
-//   _errors.cpp (true coverage, allele and error counts), sg_api_bamsort.cpp / _bamindex.cpp (the sorted truth BAM, its BAI index)
+//   _errors.cpp (true coverage, allele and error counts), sg_api_bamsort.cpp / _bamindex.cpp (the sorted truth BAM, its BAI index),
+//   sg_api_vcf.cpp (a VCF of known variants read on the device: sg_vcf_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -149,6 +150,23 @@ struct sg_ctx {
     int cur = 0;
     DevBuf refs, linear, counts, work, chunks, keys[2], vals[2], carry;
   } bamindex;
+  // a VCF of known variants (sg_vcf_*, sg_api_vcf.cpp; the rule: sg_vcf.h): `text[cur]` holds the line the last feed left
+  // unfinished (`carry` bytes) and takes the next call's text behind it, `rows[k]` the kept rows of kind k so far, `work` a
+  // call's block counts, `lines` and `frags` its line and fragment tables with their flags and scans (`scan`: the block
+  // sums), `lists` its malformed numbers and undecided fragments (the latter `last_undecided`, whose bytes are in
+  // text[cur ^ 1] until the next feed), `src` / `meta` the members of sg_vcf_feed_bgzf.  Without
+  // sg_vcf_begin nothing is kept and nothing is allocated.
+  struct Vcf {
+    bool on = false, finished = false;
+    uint32_t n_keys = 0;
+    int cur = 0;
+    uint64_t carry = 0, text_off = 0, file_off = 0;   // text_off: offset in the whole text of text[cur][0]
+    uint64_t fragments = 0, n_kind[3] = {0, 0, 0}, kept[3] = {0, 0, 0}, malformed = 0, undecided = 0, text_bytes = 0;
+    uint64_t malformed_first[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t last_undecided = 0;
+    const sg_vcf_fragment* last_list = nullptr;   // in `lists`
+    DevBuf keys, text[2], rows[3], work, lines, frags, scan, lists, info, src, meta;
+  } vcf;
   std::vector<sg_outputs*> spare;  // released output sets, reused by the next pass
   // the window planner (sg_gc_percent, sg_window_weights, sg_windows_*, sg_plan_windows / sg_plan_range;
   // sg_api_windows.cpp): `stores` holds the window weights of sg_windows_build per store id, `plan` the batch table of
@@ -277,6 +295,17 @@ struct SgSortBufs {
   uint64_t* total;
 };
 int bamsort_sort_pairs(sg_ctx* ctx, const SgSortBufs& b, uint32_t n, uint64_t k_or, uint64_t k_and);
+// BGZF input, shared by the BAM and the VCF route (sg_api_train.cpp).  bgzf_walk: the member headers of a buffer -- up to
+// `cap` whole members, *whole = the bytes they make up; a member cut by the end of the buffer ends the walk, a header
+// that is not BGZF is an error (message in *err).  inflate_launch: members of `src` (on the device) inflated to d_out +
+// member.dst, the verdicts behind the member table in `meta`.  inflate_verdicts: those verdicts, once the stream has been
+// waited for; the first member that failed names the error.
+namespace sg { struct InflateMember; }
+int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap, std::vector<sg::InflateMember>* out, uint64_t* n_out,
+              uint64_t* whole, std::string* err, uint64_t* offs = nullptr, uint32_t* bsizes = nullptr, uint32_t* isizes = nullptr);
+int inflate_launch(sg_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes, const std::vector<sg::InflateMember>& mem, DevBuf& meta, uint8_t* d_out,
+                   hipStream_t s, hipStream_t copy);
+int inflate_verdicts(sg_ctx* ctx, const std::vector<sg::InflateMember>& mem, const DevBuf& meta, const char* who);
 // no context, or a call in front of its output's X_begin
 inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
   if (!ctx) return SG_ERR_INVALID;

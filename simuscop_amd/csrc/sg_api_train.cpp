@@ -457,11 +457,13 @@ int sg_train_count(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes, const 
 // ------------------------------------------------------------------------------------------------
 // BGZF / BAM input (sg_inflate.hip, sg_bam.hip)
 // ------------------------------------------------------------------------------------------------
-namespace {
+}  // extern "C"
+
+// (bgzf_walk, inflate_launch and inflate_verdicts are declared in sg_api.h: the VCF input of sg_api_vcf.cpp goes through them too)
 // The member headers of a buffer (SAMv1 section 4.1): up to `cap` whole members; *whole = bytes they make up.  A member
 // cut by the end of the buffer ends the walk; a header that is not BGZF is an error (message in *err).
 int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap, std::vector<sg::InflateMember>* out, uint64_t* n_out,
-              uint64_t* whole, std::string* err, uint64_t* offs = nullptr, uint32_t* bsizes = nullptr, uint32_t* isizes = nullptr) {
+              uint64_t* whole, std::string* err, uint64_t* offs, uint32_t* bsizes, uint32_t* isizes) {
   uint64_t p = 0, n = 0, dst = 0;
   auto bad = [&](const char* what) {
     *err = "BGZF member at file offset " + std::to_string(file_off + p) + ": " + what;
@@ -501,6 +503,7 @@ int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap,
   return SG_OK;
 }
 
+namespace {
 const char* inflate_verdict(uint32_t v) {
   static const char* what[] = {"", "block type 3", "over-subscribed, incomplete or unused Huffman code", "distance beyond the output",
                                "DEFLATE data runs past the member", "more than 64 KiB of output", "ISIZE does not match the output",
@@ -515,6 +518,8 @@ const char* bam_verdict(uint32_t v) {
     default: return "l_read_name of 0 or a negative l_seq";
   }
 }
+
+}  // namespace
 
 // Members of `src` (already on the device) inflated to d_out + member.dst; the verdicts land in meta behind the member table.
 int inflate_launch(sg_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes, const std::vector<sg::InflateMember>& mem, DevBuf& meta, uint8_t* d_out,
@@ -551,7 +556,8 @@ int inflate_verdicts(sg_ctx* ctx, const std::vector<sg::InflateMember>& mem, con
       return ctx->fail(SG_ERR_INVALID, std::string(who) + ": BGZF member at file offset " + std::to_string(mem[i].file_off) + ": " + inflate_verdict(st[i]));
   return SG_OK;
 }
-}  // namespace
+
+extern "C" {
 
 int sg_bgzf_members(const void* buf, uint64_t bytes, uint64_t* offsets, uint32_t* bsize, uint32_t* isize, uint64_t cap, uint64_t* n_members,
                     uint64_t* whole_bytes) {
