@@ -767,6 +767,45 @@ int sg_sub_row_identity_first(const double cdf4[4], int cd, uint64_t cum[3], uin
 uint32_t sg_row_symbols(const double* cdf, int n);
 int sg_alias_row(const double* cdf, int n, uint32_t lgW, uint32_t* thr, uint8_t* lo, uint8_t* hi);
 
+/* ---- truthEval: an aligner's BAM scored against the truth BAM (the rule: csrc/sg_eval.h) ----
+ * Both files are fed as whole BGZF members in file order, from the file's first byte, as sg_train_feed_bgzf takes them (the
+ * same walk, inflate, record boundaries, carry of a record that straddles calls, and refusals with the file or decompressed
+ * offset); `bytes` = 0 ends a stream and refuses a record left unfinished.  One session per context:
+ *   sg_eval_begin        n_ref_truth references in the truth's header, whose first record starts first_record_skip bytes into
+ *                        the decompressed stream.  key_bits 1..64: the bits of a read's key that are kept (64 in use; fewer
+ *                        make collisions common, for tests).  min_overlap 1..100: PCT of the `near` category
+ *   sg_eval_truth_bgzf   the truth's members: a row per record (key, name, refID, POS, span, strand / unmapped / class / mate),
+ *                        the names in an arena on the device.  At most 2^32 - 1025 records
+ *   sg_eval_truth_done   sorts the rows by key, marks every (name, mate) the truth holds more than once; *records, *duplicates
+ *                        = rows, rows so marked
+ *   sg_eval_test_refmap  map[i] = the truth's refID of the test file's reference i (by @SQ name), -1 for none; and where the
+ *                        test file's first record starts
+ *   sg_eval_test_bgzf    the test file's members: look-up, claim (the least ordinal in the file wins a truth read), score
+ *   sg_eval_finish       counts the truth reads nobody claimed and returns the table, SG_EVAL_CELLS cells laid out
+ *                        [mate 0..1][class: plain, edited, unmapped][MAPQ 0..255][category: exact, near, wrong_place,
+ *                        wrong_strand, wrong_contig, lost, invented, both_unmapped], and the counts
+ *   sg_eval_end          ends the session and frees its buffers
+ *   sg_eval_classify, sg_eval_key  host only, no context: the category (0..7 in the order above) of one pair, the key of one
+ *                        read -- the same code the kernels run */
+#define SG_EVAL_CELLS 12288
+typedef struct sg_eval_counts {
+  uint64_t test_records, secondary, supplementary, unknown, ambiguous, repeated, truth_records, truth_duplicates;
+  uint64_t missing[6];                 /* [mate][class] */
+  uint64_t truth_bytes, test_bytes;    /* inflated */
+  double t_inflate, t_truth, t_sort, t_test;   /* seconds: inflate and boundaries of both files (part of the next two); the truth's
+                                                  calls; sg_eval_truth_done; the test file's calls */
+} sg_eval_counts;
+int sg_eval_begin(sg_ctx* ctx, uint32_t n_ref_truth, uint32_t key_bits, uint32_t min_overlap, uint64_t first_record_skip);
+int sg_eval_truth_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes);
+int sg_eval_truth_done(sg_ctx* ctx, uint64_t* records, uint64_t* duplicates);
+int sg_eval_test_refmap(sg_ctx* ctx, const int32_t* map, uint32_t n_ref_test, uint64_t first_record_skip);
+int sg_eval_test_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes);
+int sg_eval_finish(sg_ctx* ctx, uint64_t* table, uint64_t cap, sg_eval_counts* counts);
+void sg_eval_end(sg_ctx* ctx);
+uint32_t sg_eval_classify(int32_t truth_ref, int64_t truth_pos, uint64_t truth_span, int truth_reverse, int truth_unmapped, int32_t test_ref,
+                          int64_t test_pos, uint64_t test_span, int test_reverse, int test_unmapped, uint32_t min_overlap);
+uint64_t sg_eval_key(const void* name, uint32_t len, uint32_t mate, uint32_t key_bits);
+
 /* ---- a VCF of known variants, read on the device: the rows lib/vcfparser/vcfparser.cpp:26-106 yields ----
  * The text -- plain, or the members of a BGZF file as bgzip writes them -- is cut into the fragments the parser's
  * fgets(buf, 20000) returns, and every fragment gets the parser's verdict: skipped, an SNV, an insertion or a deletion with

@@ -15,6 +15,7 @@ LIB_DIR = os.path.join(PKG_DIR, "lib")
 ENGINE_SO = os.path.join(LIB_DIR, "libsimuscop_amd.so")
 HOST_SO = os.path.join(LIB_DIR, "libsimuscop_host.so")
 SIMUREADS = os.path.join(LIB_DIR, "simuReads")
+TRUTHEVAL = os.path.join(LIB_DIR, "truthEval")
 
 SG_K_NAMES = ["plan", "namebase", "indel", "scan", "emit", "emit_slow"]
 
@@ -40,6 +41,8 @@ ENGINE_SYMBOLS = [
     "sg_variants_begin", "sg_variants_add", "sg_variants_counts", "sg_variants_reset", "sg_variants_info", "sg_variants_end",
     "sg_variant_observe",
     "sg_errtab_begin", "sg_errtab_add", "sg_errtab_counts", "sg_errtab_reset", "sg_errtab_info", "sg_errtab_end", "sg_errtab_observe",
+    "sg_eval_begin", "sg_eval_truth_bgzf", "sg_eval_truth_done", "sg_eval_test_refmap", "sg_eval_test_bgzf", "sg_eval_finish", "sg_eval_end",
+    "sg_eval_classify", "sg_eval_key",
     "sg_vcf_begin", "sg_vcf_feed", "sg_vcf_feed_bgzf", "sg_vcf_undecided", "sg_vcf_finish", "sg_vcf_rows", "sg_vcf_end", "sg_vcf_row",
 ]
 
@@ -64,6 +67,19 @@ class SgTrainSetup(C.Structure):
                 ("snv_homo", C.POINTER(C.c_uint8)),
                 ("n_ins", C.c_uint64), ("ins_contig", C.POINTER(C.c_uint32)), ("ins_pos", C.POINTER(C.c_int64)), ("ins_len", C.POINTER(C.c_int32)),
                 ("n_del", C.c_uint64), ("del_contig", C.POINTER(C.c_uint32)), ("del_pos", C.POINTER(C.c_int64)), ("del_len", C.POINTER(C.c_int32))]
+
+
+class SgEvalCounts(C.Structure):
+    """sg_eval_counts (include/simuscop_amd.h)"""
+    _fields_ = [("test_records", C.c_uint64), ("secondary", C.c_uint64), ("supplementary", C.c_uint64), ("unknown", C.c_uint64),
+                ("ambiguous", C.c_uint64), ("repeated", C.c_uint64), ("truth_records", C.c_uint64), ("truth_duplicates", C.c_uint64),
+                ("missing", C.c_uint64 * 6), ("truth_bytes", C.c_uint64), ("test_bytes", C.c_uint64),
+                ("t_inflate", C.c_double), ("t_truth", C.c_double), ("t_sort", C.c_double), ("t_test", C.c_double)]
+
+
+SG_EVAL_CELLS = 12288
+EVAL_CATEGORIES = ["exact", "near", "wrong_place", "wrong_strand", "wrong_contig", "lost", "invented", "both_unmapped"]
+EVAL_CLASSES = ["plain", "edited", "unmapped"]
 
 
 class SgProfileCdf(C.Structure):
@@ -352,6 +368,18 @@ def load_engine():
     lib.sg_errtab_end.argtypes = [vp]
     lib.sg_errtab_observe.argtypes = [u8p, C.c_uint32, C.c_int, u32p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.c_uint32, u64p, C.c_uint64]
+    lib.sg_eval_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
+    lib.sg_eval_truth_bgzf.argtypes = [vp, C.c_char_p, C.c_uint64]
+    lib.sg_eval_truth_done.argtypes = [vp, u64p, u64p]
+    lib.sg_eval_test_refmap.argtypes = [vp, C.POINTER(C.c_int32), C.c_uint32, C.c_uint64]
+    lib.sg_eval_test_bgzf.argtypes = [vp, C.c_char_p, C.c_uint64]
+    lib.sg_eval_finish.argtypes = [vp, u64p, C.c_uint64, C.POINTER(SgEvalCounts)]
+    lib.sg_eval_end.argtypes = [vp]
+    lib.sg_eval_end.restype = None
+    lib.sg_eval_classify.argtypes = [C.c_int32, C.c_int64, C.c_uint64, C.c_int, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_int, C.c_int, C.c_uint32]
+    lib.sg_eval_classify.restype = C.c_uint32
+    lib.sg_eval_key.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.sg_eval_key.restype = C.c_uint64
     lib.sg_vcf_begin.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint32]
     lib.sg_vcf_feed.argtypes = [vp, C.c_char_p, C.c_uint64]
     lib.sg_vcf_feed_bgzf.argtypes = [vp, C.c_char_p, C.c_uint64]
@@ -485,6 +513,36 @@ def train_profile(ref: str, vcf: str, output: str, sam: str = "", bam: str = "",
     rc = lib.simu_train(C.byref(o), C.byref(st), err, len(err))
     if rc != 0:
         raise SimuError(f"seqToProfile failed (exit code {rc}): {err.value.decode(errors='replace')}")
+    return st
+
+
+class SimuEvalOptions(C.Structure):
+    """simu_eval_options (host/eval.h)"""
+    _fields_ = [("truth", C.c_char_p), ("bam", C.c_char_p), ("output", C.c_char_p), ("min_overlap", C.c_int32), ("device", C.c_int32),
+                ("threads", C.c_int32), ("quiet", C.c_int32)]
+
+
+class SimuEvalStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("test_records", "secondary", "supplementary", "unknown", "ambiguous", "repeated", "truth_records",
+                                         "truth_duplicates", "scored", "missing", "truth_bgzf_bytes", "test_bgzf_bytes", "truth_bytes", "test_bytes")] + \
+               [(n, C.c_double) for n in ("t_inflate", "t_truth", "t_sort", "t_test", "t_total")]
+
+
+def truth_eval(truth: str, bam: str, output: str = "", min_overlap: int = 10, device: int = 0, quiet: int = 1) -> SimuEvalStats:
+    """`truthEval` in-process (host/eval.h): the aligner's `bam` scored against the `truth` BAM; eval.tsv goes to `output`."""
+    lib = load_host()
+    lib.simu_eval_default_options.argtypes = [C.POINTER(SimuEvalOptions)]
+    lib.simu_eval_default_options.restype = None
+    lib.simu_eval.argtypes = [C.POINTER(SimuEvalOptions), C.POINTER(SimuEvalStats), C.c_char_p, C.c_size_t]
+    o = SimuEvalOptions()
+    lib.simu_eval_default_options(C.byref(o))
+    o.truth, o.bam, o.output = truth.encode(), bam.encode(), output.encode()
+    o.min_overlap, o.device, o.quiet = min_overlap, device, quiet
+    st = SimuEvalStats()
+    err = C.create_string_buffer(4096)
+    rc = lib.simu_eval(C.byref(o), C.byref(st), err, len(err))
+    if rc != 0:
+        raise SimuError(f"truthEval failed (exit code {rc}): {err.value.decode(errors='replace')}")
     return st
 
 

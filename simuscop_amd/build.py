@@ -4,6 +4,7 @@
   libsimuscop_host.so -- C++ host side mirroring SimuSCoP's config/CLI surface      (g++)
   simuReads           -- `simuReads <config.txt>` command line, links the two above  (g++)
   seqToProfile        -- the profile trainer's command line (host/train_main.cpp)     (g++)
+  truthEval           -- an aligner's BAM scored against the truth BAM (host/eval_main.cpp) (g++)
 """
 from __future__ import annotations
 
@@ -18,12 +19,13 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
-ENGINE_SRCS = ["sg_kernels.hip", "sg_emit_fast.hip", "sg_scan.hip", "sg_windows.hip", "sg_haplotypes.hip", "sg_deflate.hip", "sg_train.hip", "sg_inflate.hip", "sg_bam.hip", "sg_truth.hip", "sg_truth_tags.hip", "sg_bamsort.hip", "sg_bamindex.hip", "sg_depth.hip", "sg_variants.hip", "sg_errors.hip", "sg_vcf.hip", "sg_memory.cpp", "sg_api.cpp", "sg_profile_tables.cpp", "sg_api_deflate.cpp", "sg_api_truth.cpp", "sg_api_haplotypes.cpp", "sg_api_windows.cpp", "sg_api_train.cpp", "sg_api_depth.cpp", "sg_api_variants.cpp", "sg_api_errors.cpp", "sg_api_truth_tags.cpp", "sg_api_bamsort.cpp", "sg_api_bamindex.cpp", "sg_api_vcf.cpp", "sg_tables.cpp", "sg_deflate.cpp"]
+ENGINE_SRCS = ["sg_kernels.hip", "sg_emit_fast.hip", "sg_scan.hip", "sg_windows.hip", "sg_haplotypes.hip", "sg_deflate.hip", "sg_train.hip", "sg_inflate.hip", "sg_bam.hip", "sg_truth.hip", "sg_truth_tags.hip", "sg_bamsort.hip", "sg_bamindex.hip", "sg_depth.hip", "sg_variants.hip", "sg_errors.hip", "sg_vcf.hip", "sg_eval.hip", "sg_memory.cpp", "sg_api.cpp", "sg_profile_tables.cpp", "sg_api_deflate.cpp", "sg_api_truth.cpp", "sg_api_haplotypes.cpp", "sg_api_windows.cpp", "sg_api_train.cpp", "sg_api_depth.cpp", "sg_api_variants.cpp", "sg_api_errors.cpp", "sg_api_truth_tags.cpp", "sg_api_bamsort.cpp", "sg_api_bamindex.cpp", "sg_api_vcf.cpp", "sg_api_eval.cpp", "sg_tables.cpp", "sg_deflate.cpp"]
 HOST_SRCS = ["host/config.cpp", "host/profile.cpp", "host/fasta.cpp", "host/variants.cpp", "host/genome.cpp",
              "host/simulate.cpp", "host/truth_outputs.cpp", "host/truth_variants.cpp", "host/truth_errors.cpp", "host/truth_sort.cpp", "host/truth_sort_tiles.cpp", "host/truth_index.cpp",
-             "host/train.cpp"]
+             "host/train.cpp", "host/eval.cpp"]
 CLI_SRCS = ["host/main.cpp"]
 TRAIN_CLI_SRCS = ["host/train_main.cpp"]
+EVAL_CLI_SRCS = ["host/eval_main.cpp"]
 
 
 def _newer(target, deps):
@@ -85,6 +87,14 @@ def build_host(force=False, verbose=False):
     if force or _newer(texe, tcli + hdrs + [so]):
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", CSRC] + tcli + \
               ["-o", texe, "-L", LIBDIR, "-lsimuscop_host", "-lsimuscop_amd", "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    eexe = os.path.join(LIBDIR, "truthEval")
+    ecli = [os.path.join(CSRC, s) for s in EVAL_CLI_SRCS]
+    if force or _newer(eexe, ecli + hdrs + [so]):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", CSRC] + ecli + \
+              ["-o", eexe, "-L", LIBDIR, "-lsimuscop_host", "-lsimuscop_amd", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

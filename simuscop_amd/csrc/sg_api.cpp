@@ -257,6 +257,7 @@ int sg_create(sg_ctx** out, int device, uint64_t seed) {
 void sg_destroy(sg_ctx* ctx) {
   if (!ctx) return;
   sg_train_end(ctx);
+  sg_eval_end(ctx);
   delete ctx;
 }
 

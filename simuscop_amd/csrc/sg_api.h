@@ -8,7 +8,7 @@
 //   sg_api_haplotypes.cpp  reference ingest and haplotype assembly: sg_reference_*, sg_build / upload_haplotypes, sg_haplotype_codes
 //   sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM input), sg_api_depth.cpp / _variants.cpp /
 //   _errors.cpp (true coverage, allele and error counts), sg_api_bamsort.cpp / _bamindex.cpp (the sorted truth BAM, its BAI index),
-//   sg_api_vcf.cpp (a VCF of known variants read on the device: sg_vcf_*)
+//   sg_api_vcf.cpp (a VCF of known variants read on the device: sg_vcf_*), sg_api_eval.cpp (truthEval: sg_eval_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include <utility>
 #include <vector>
 
+#include "sg_bam.h"
 #include "sg_device.h"
 #include "sg_haplotypes.h"
 
@@ -51,6 +52,7 @@ extern thread_local std::string g_create_error;   // sg_last_error(nullptr): cal
 
 struct sg_outputs;
 struct sg_train_session;
+struct sg_eval_session;
 
 struct sg_ctx {
   int device = 0;
@@ -191,6 +193,7 @@ struct sg_ctx {
   } win;
   uint64_t ref_raw_bytes = 0;
   sg_train_session* train = nullptr;   // profile training in progress (sg_train_begin .. sg_train_finish / sg_train_end)
+  sg_eval_session* eval = nullptr;     // truthEval in progress (sg_eval_begin .. sg_eval_end; sg_api_eval.cpp)
   std::vector<sg::DevContig> ref_contigs;  // host copy of the committed contig table
   uint64_t* mail = nullptr;   // pinned: where a pass's totals[0..4] land (copied into `pass` when it is settled)
   // A batch and its sampling pass: the stage, and every fact whose meaning ends with the pass.  The buffers those facts
@@ -306,6 +309,38 @@ int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap,
 int inflate_launch(sg_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes, const std::vector<sg::InflateMember>& mem, DevBuf& meta, uint8_t* d_out,
                    hipStream_t s, hipStream_t copy);
 int inflate_verdicts(sg_ctx* ctx, const std::vector<sg::InflateMember>& mem, const DevBuf& meta, const char* who);
+// A BAM file fed as whole BGZF members in file order (sg_api_train.cpp): what sg_train_feed_bgzf and the sg_eval_*_bgzf calls
+// share.  A call goes
+//   bam_stream_stage    the member walk and its refusals; the members start for the device on `copy` (wait for it before the
+//                       caller's buffer is let go)
+//   bam_stream_records  the members inflated into stream[scur] behind the partial record the call before left (`carry` bytes),
+//                       the header passed over (`skip`), record boundaries and the inflate / boundary refusals; `job` holds the
+//                       stream and, queued on `s`, the start of each of its n_rec whole records
+//   (the caller's own kernels over job->rec; a record they refuse: bam_stream_record_error with their error key)
+//   bam_stream_advance  the partial record behind the last whole one goes to the front of the other stream buffer
+// and bam_stream_close, at the end of the file, refuses a record left unfinished.  bam_stream_start names the references
+// (refID order; ref_names may be NULL when no kernel prints them) and where the first record starts.
+struct SgBamStream {
+  uint32_t n_ref = 0;
+  uint64_t skip = 0;         // header bytes of the decompressed stream still to be passed over
+  uint64_t carry = 0;
+  uint64_t file_off = 0;     // file offset of the next member
+  uint64_t stream_off = 0;   // offset in the decompressed stream of stream[scur][0]
+  uint64_t records = 0, inflated = 0;
+  int scur = 0;
+  DevBuf names, name_off, src, meta, stream[2], seg, rec, scan, totals;
+  // of the call in progress
+  std::vector<sg::InflateMember> mem;
+  uint64_t bytes = 0, total = 0, L = 0, tail = 0, n_rec = 0;
+};
+int bam_stream_start(sg_ctx* ctx, SgBamStream& B, const char* const* ref_names, uint32_t n_ref, uint64_t first_record_skip);
+int bam_stream_stage(sg_ctx* ctx, SgBamStream& B, const char* who, const void* members, uint64_t bytes, hipStream_t copy);
+int bam_stream_records(sg_ctx* ctx, SgBamStream& B, const char* who, hipStream_t s, hipStream_t copy, sg::BamJob* job);
+int bam_stream_record_error(sg_ctx* ctx, const SgBamStream& B, const char* who, uint64_t key);
+int bam_stream_advance(sg_ctx* ctx, SgBamStream& B, hipStream_t s);
+int bam_stream_close(sg_ctx* ctx, const SgBamStream& B, const char* who);
+// a device buffer grown with its first keep_bytes kept (sg_api_train.cpp)
+int sg_grow_keep(sg_ctx* ctx, DevBuf& buf, size_t keep_bytes, size_t want_bytes);
 // no context, or a call in front of its output's X_begin
 inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
   if (!ctx) return SG_ERR_INVALID;

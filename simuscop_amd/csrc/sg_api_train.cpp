@@ -41,18 +41,12 @@ struct sg_train_session {
   uint64_t windows_cap = 0;          // rows the window arrays hold
   sg::TrainCarry* mail = nullptr;    // pinned: the carry a chunk left, the flag word behind it
   uint32_t* mail_flags() { return (uint32_t*)(mail + 1); }
-  // BAM input (sg_train_bam_start, sg_train_feed_bgzf): members are inflated into stream[scur] behind the partial record the
-  // call before left there (bam_carry bytes); the lines of the whole records are rendered into the text buffers above
+  // BAM input (sg_train_bam_start, sg_train_feed_bgzf): the members come in through `in` (SgBamStream, sg_api.h); the lines of
+  // its whole records are rendered into the text buffers above
   bool bam = false;
-  uint32_t n_ref = 0;
-  uint64_t bam_skip = 0;             // header bytes of the decompressed stream still to be passed over
-  uint64_t bam_carry = 0;
-  uint64_t bam_file_off = 0;         // file offset of the next member
-  uint64_t bam_stream_off = 0;       // offset in the decompressed stream of stream[scur][0]
-  uint64_t bam_records = 0, bam_inflated = 0;
+  SgBamStream in;                    // the members, the stream and its record starts (sg_api.h)
   double bam_seconds = 0;
-  int scur = 0;
-  DevBuf names, name_off, bgzf_src, bgzf_meta, stream[2], seg, rec, line_len, line_off, bam_scan, bam_totals;
+  DevBuf line_len, line_off;
   ~sg_train_session() {   // (the buffers go with their members)
     if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
     if (mail) (void)hipHostFree(mail);
@@ -244,9 +238,10 @@ int sg_train_begin(sg_ctx* ctx, const sg_train_setup* st) {
   return SG_OK;
 }
 
-namespace {
-// a device buffer grown with what it holds kept (the window arrays live across chunks)
-int grow_keep(sg_ctx* ctx, DevBuf& buf, size_t keep_bytes, size_t want_bytes) {
+}  // extern "C"
+// a device buffer grown with what it holds kept (the window arrays live across chunks, a stream's carried record and
+// an evaluation's rows across calls); declared in sg_api.h
+int sg_grow_keep(sg_ctx* ctx, DevBuf& buf, size_t keep_bytes, size_t want_bytes) {
   if (want_bytes <= buf.cap) return SG_OK;
   DevBuf bigger;
   SG_ENSURE(bigger, want_bytes + want_bytes / 2);
@@ -255,7 +250,8 @@ int grow_keep(sg_ctx* ctx, DevBuf& buf, size_t keep_bytes, size_t want_bytes) {
   buf = std::move(bigger);
   return SG_OK;
 }
-
+extern "C" {
+namespace {
 void train_job(sg_ctx* ctx, sg_train_session* T, sg::TrainJob& J) {
   memset(&J, 0, sizeof J);
   J.keys = T->keys.as<char>();
@@ -318,8 +314,8 @@ int train_run_chunk(sg_ctx* ctx, sg_train_session* T, uint64_t bytes) {
     const uint64_t want = T->n_windows + n_lines + 1;
     if (want > T->windows_cap) {
       const uint64_t cap = want + want / 2;
-      if ((rc = grow_keep(ctx, T->windows, T->n_windows * sizeof(sg::TrainWindow), cap * sizeof(sg::TrainWindow))) != SG_OK) return rc;
-      if ((rc = grow_keep(ctx, T->window_rc, T->n_windows * 4, cap * 4)) != SG_OK) return rc;
+      if ((rc = sg_grow_keep(ctx, T->windows, T->n_windows * sizeof(sg::TrainWindow), cap * sizeof(sg::TrainWindow))) != SG_OK) return rc;
+      if ((rc = sg_grow_keep(ctx, T->window_rc, T->n_windows * 4, cap * 4)) != SG_OK) return rc;
       SG_HIP(hipMemsetAsync(T->window_rc.as<uint32_t>() + T->n_windows, 0, (cap - T->n_windows) * 4, s));
       T->windows_cap = cap;
     }
@@ -459,7 +455,8 @@ int sg_train_count(sg_ctx* ctx, const char* sam_text, uint64_t sam_bytes, const 
 // ------------------------------------------------------------------------------------------------
 }  // extern "C"
 
-// (bgzf_walk, inflate_launch and inflate_verdicts are declared in sg_api.h: the VCF input of sg_api_vcf.cpp goes through them too)
+// (bgzf_walk, inflate_launch, inflate_verdicts and the bam_stream_* calls are declared in sg_api.h: the VCF input of
+// sg_api_vcf.cpp and the two files of sg_api_eval.cpp go through them too)
 // The member headers of a buffer (SAMv1 section 4.1): up to `cap` whole members; *whole = bytes they make up.  A member
 // cut by the end of the buffer ends the walk; a header that is not BGZF is an error (message in *err).
 int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap, std::vector<sg::InflateMember>* out, uint64_t* n_out,
@@ -557,6 +554,131 @@ int inflate_verdicts(sg_ctx* ctx, const std::vector<sg::InflateMember>& mem, con
   return SG_OK;
 }
 
+// ---- SgBamStream (sg_api.h): what sg_train_feed_bgzf and the sg_eval_*_bgzf calls share ----
+int bam_stream_start(sg_ctx* ctx, SgBamStream& B, const char* const* ref_names, uint32_t n_ref, uint64_t first_record_skip) {
+  std::string names;
+  std::vector<uint64_t> off(n_ref + 1, 0);
+  for (uint32_t i = 0; i < n_ref; i++) {
+    if (ref_names && !ref_names[i]) return SG_ERR_INVALID;
+    off[i] = names.size();
+    if (ref_names) names += ref_names[i];
+    names += '\0';
+  }
+  off[n_ref] = names.size();
+  SG_ENSURE(B.names, names.size() + 64);
+  SG_ENSURE(B.name_off, off.size() * 8 + 64);
+  if (!names.empty()) SG_HIP(hipMemcpy(B.names.p, names.data(), names.size(), hipMemcpyHostToDevice));
+  SG_HIP(hipMemcpy(B.name_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+  SG_ENSURE(B.totals, 64);
+  B.n_ref = n_ref;
+  B.skip = first_record_skip;
+  B.carry = B.file_off = B.stream_off = B.records = B.inflated = 0;
+  B.scur = 0;
+  return SG_OK;
+}
+
+int bam_stream_stage(sg_ctx* ctx, SgBamStream& B, const char* who, const void* members, uint64_t bytes, hipStream_t copy) {
+  uint64_t n = 0, whole = 0;
+  std::string err;
+  B.mem.clear();
+  B.total = 0;
+  if (bgzf_walk((const uint8_t*)members, bytes, B.file_off, ~0ull, &B.mem, &n, &whole, &err) != SG_OK)
+    return ctx->fail(SG_ERR_INVALID, std::string(who) + ": " + err);
+  if (whole != bytes)
+    return ctx->fail(SG_ERR_INVALID, std::string(who) + ": BGZF member at file offset " + std::to_string(B.file_off + whole) +
+                                         " is cut short (truncated file?)");
+  for (sg::InflateMember& m : B.mem) { m.dst += B.carry; B.total += m.isize; }
+  B.bytes = bytes;
+  SG_ENSURE(B.src, bytes + 64);
+  SG_HIP(hipMemcpyAsync(B.src.p, members, bytes, hipMemcpyHostToDevice, copy));
+  return SG_OK;
+}
+
+int bam_stream_record_error(sg_ctx* ctx, const SgBamStream& B, const char* who, uint64_t key) {
+  return ctx->fail(SG_ERR_INVALID, std::string(who) + ": BAM record at decompressed offset " + std::to_string(B.stream_off + (key >> 8)) + ": " +
+                                       bam_verdict((uint32_t)(key & 0xFF)));
+}
+
+int bam_stream_records(sg_ctx* ctx, SgBamStream& B, const char* who, hipStream_t s, hipStream_t copy, sg::BamJob* job) {
+  const uint64_t carry = B.carry, L = carry + B.total;
+  DevBuf& S = B.stream[B.scur];
+  int rc;
+  if ((rc = sg_grow_keep(ctx, S, carry, L + 64)) != SG_OK) return rc;
+  if ((rc = inflate_launch(ctx, B.src.as<uint8_t>(), B.bytes, B.mem, B.meta, S.as<uint8_t>(), s, copy)) != SG_OK) return rc;
+  // ---- record boundaries ----
+  uint64_t base = 0;
+  if (B.skip) {   // (the header: nothing is carried while it lasts)
+    base = std::min(B.skip, L);
+    B.skip -= base;
+  }
+  const uint32_t n_seg = L > base ? (uint32_t)((L - base + sg::kBamSegment - 1) / sg::kBamSegment) : 0;
+  SG_ENSURE(B.seg, (size_t)n_seg * 28 + 64);
+  SG_ENSURE(B.scan, (size_t)(sg::scan_blocks(std::max<uint32_t>(n_seg, 1)) + 1) * 8 + 64);
+  sg::BamJob& J = *job;
+  memset(&J, 0, sizeof J);
+  J.d = S.as<uint8_t>();
+  J.base = base;
+  J.L = L;
+  J.n_ref = B.n_ref;
+  J.names = B.names.as<char>();
+  J.name_off = B.name_off.as<uint64_t>();
+  J.n_seg = n_seg;
+  J.guess = B.seg.as<uint64_t>();
+  J.exit = J.guess + n_seg;
+  J.first = J.exit + n_seg;
+  J.count = (uint32_t*)(J.first + n_seg);
+  J.scan_bsum = B.scan.as<uint64_t>();
+  J.totals = B.totals.as<uint64_t>();
+  uint64_t h_tot[4] = {0, 0, base, ~0ull};
+  SG_HIP(hipMemcpyAsync(J.totals, h_tot, 32, hipMemcpyHostToDevice, s));
+  if (n_seg) {
+    sg::launch_bam_guess(J, s);
+    sg::launch_bam_verify(J, s);
+    sg::launch_scan_u32(J.count, n_seg, J.scan_bsum, J.first, J.totals, s);
+  }
+  SG_HIP(hipGetLastError());
+  SG_HIP(hipMemcpyAsync(h_tot, J.totals, 32, hipMemcpyDeviceToHost, s));
+  SG_HIP(hipStreamSynchronize(s));
+  if ((rc = inflate_verdicts(ctx, B.mem, B.meta, who)) != SG_OK) return rc;
+  if (h_tot[3] != ~0ull) return bam_stream_record_error(ctx, B, who, h_tot[3]);
+  const uint64_t n_rec = h_tot[0];
+  B.tail = h_tot[2];
+  B.L = L;
+  B.n_rec = n_rec;
+  if (n_rec) {
+    SG_ENSURE(B.rec, n_rec * 8 + 64);
+    SG_ENSURE(B.scan, (size_t)(sg::scan_blocks((uint32_t)n_rec) + 1) * 8 + 64);
+    J.scan_bsum = B.scan.as<uint64_t>();
+    J.rec = B.rec.as<uint64_t>();
+    J.n_rec = n_rec;
+    sg::launch_bam_starts(J, s);
+  }
+  return SG_OK;
+}
+
+int bam_stream_advance(sg_ctx* ctx, SgBamStream& B, hipStream_t s) {
+  // the partial record behind the last whole one goes to the front of the other stream buffer
+  const uint64_t left = B.L - B.tail;
+  DevBuf& S = B.stream[B.scur];
+  DevBuf& N = B.stream[B.scur ^ 1];
+  SG_ENSURE(N, left + 64);
+  if (left) SG_HIP(hipMemcpyAsync(N.p, S.as<uint8_t>() + B.tail, left, hipMemcpyDeviceToDevice, s));
+  B.scur ^= 1;
+  B.carry = left;
+  B.stream_off += B.tail;
+  B.file_off += B.bytes;
+  B.records += B.n_rec;
+  B.inflated += B.total;
+  return SG_OK;
+}
+
+int bam_stream_close(sg_ctx* ctx, const SgBamStream& B, const char* who) {
+  if (B.carry)
+    return ctx->fail(SG_ERR_INVALID, std::string(who) + ": the BAM record at decompressed offset " + std::to_string(B.stream_off) +
+                                         " runs past the end of the stream");
+  return SG_OK;
+}
+
 extern "C" {
 
 int sg_bgzf_members(const void* buf, uint64_t bytes, uint64_t* offsets, uint32_t* bsize, uint32_t* isize, uint64_t cap, uint64_t* n_members,
@@ -600,23 +722,8 @@ int sg_train_bam_start(sg_ctx* ctx, const char* const* ref_names, uint32_t n_ref
   if (!T) return ctx->fail(SG_ERR_INVALID, "sg_train_bam_start: call sg_train_begin first");
   if (T->fed || T->bam) return ctx->fail(SG_ERR_INVALID, "sg_train_bam_start: call it once, before anything is fed");
   SG_HIP(hipSetDevice(ctx->device));
-  std::string names;
-  std::vector<uint64_t> off(n_ref + 1, 0);
-  for (uint32_t i = 0; i < n_ref; i++) {
-    if (!ref_names[i]) return SG_ERR_INVALID;
-    off[i] = names.size();
-    names += ref_names[i];
-    names += '\0';
-  }
-  off[n_ref] = names.size();
-  SG_ENSURE(T->names, names.size() + 64);
-  SG_ENSURE(T->name_off, off.size() * 8 + 64);
-  if (!names.empty()) SG_HIP(hipMemcpy(T->names.p, names.data(), names.size(), hipMemcpyHostToDevice));
-  SG_HIP(hipMemcpy(T->name_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-  SG_ENSURE(T->bam_totals, 64);
+  if (int rc = bam_stream_start(ctx, T->in, ref_names, n_ref, first_record_skip)) return rc;
   T->bam = true;
-  T->n_ref = n_ref;
-  T->bam_skip = first_record_skip;
   return SG_OK;
 }
 
@@ -631,91 +738,29 @@ int sg_train_feed_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes) {
   if (!bytes) {   // the end of the stream: nothing may be left of a record
     const int rc = train_settle(ctx, T);
     if (rc != SG_OK || T->capped) return rc;
-    if (T->bam_carry)
-      return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: the BAM record at decompressed offset " + std::to_string(T->bam_stream_off) +
-                                           " runs past the end of the stream");
-    return SG_OK;
+    return bam_stream_close(ctx, T->in, "sg_train_feed_bgzf");
   }
-  std::vector<sg::InflateMember> mem;
-  uint64_t n = 0, whole = 0, total = 0;
-  std::string err;
-  if (bgzf_walk((const uint8_t*)members, bytes, T->bam_file_off, ~0ull, &mem, &n, &whole, &err) != SG_OK)
-    return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: " + err);
-  if (whole != bytes)
-    return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: BGZF member at file offset " + std::to_string(T->bam_file_off + whole) +
-                                         " is cut short (truncated file?)");
-  const uint64_t carry = T->bam_carry;
-  for (sg::InflateMember& m : mem) { m.dst += carry; total += m.isize; }
-  const uint64_t L = carry + total;
   // stage the members while the chunk before is still counted
-  SG_ENSURE(T->bgzf_src, bytes + 64);
-  SG_HIP(hipMemcpyAsync(T->bgzf_src.p, members, bytes, hipMemcpyHostToDevice, T->copy_stream));
-  int rc = train_settle(ctx, T);
+  int rc = bam_stream_stage(ctx, T->in, "sg_train_feed_bgzf", members, bytes, T->copy_stream);
+  if (rc != SG_OK) return rc;
+  rc = train_settle(ctx, T);
   SG_HIP(hipStreamSynchronize(T->copy_stream));   // the caller's buffer is free again when this returns
   if (rc != SG_OK) return rc;
   if (T->capped) return SG_OK;
-  DevBuf& S = T->stream[T->scur];
-  if ((rc = grow_keep(ctx, S, carry, L + 64)) != SG_OK) return rc;
-  if ((rc = inflate_launch(ctx, T->bgzf_src.as<uint8_t>(), bytes, mem, T->bgzf_meta, S.as<uint8_t>(), s, T->copy_stream)) != SG_OK) return rc;
-  // ---- record boundaries ----
-  uint64_t base = 0;
-  if (T->bam_skip) {   // (the header: nothing is carried while it lasts)
-    base = std::min(T->bam_skip, L);
-    T->bam_skip -= base;
-  }
-  const uint32_t n_seg = L > base ? (uint32_t)((L - base + sg::kBamSegment - 1) / sg::kBamSegment) : 0;
-  SG_ENSURE(T->seg, (size_t)n_seg * 28 + 64);
-  SG_ENSURE(T->bam_scan, (size_t)(sg::scan_blocks(std::max<uint32_t>(n_seg, 1)) + 1) * 8 + 64);
   sg::BamJob J;
-  memset(&J, 0, sizeof J);
-  J.d = S.as<uint8_t>();
-  J.base = base;
-  J.L = L;
-  J.n_ref = T->n_ref;
-  J.names = T->names.as<char>();
-  J.name_off = T->name_off.as<uint64_t>();
-  J.n_seg = n_seg;
-  J.guess = T->seg.as<uint64_t>();
-  J.exit = J.guess + n_seg;
-  J.first = J.exit + n_seg;
-  J.count = (uint32_t*)(J.first + n_seg);
-  J.scan_bsum = T->bam_scan.as<uint64_t>();
-  J.totals = T->bam_totals.as<uint64_t>();
-  uint64_t h_tot[4] = {0, 0, base, ~0ull};
-  SG_HIP(hipMemcpyAsync(J.totals, h_tot, 32, hipMemcpyHostToDevice, s));
-  if (n_seg) {
-    sg::launch_bam_guess(J, s);
-    sg::launch_bam_verify(J, s);
-    sg::launch_scan_u32(J.count, n_seg, J.scan_bsum, J.first, J.totals, s);
-  }
-  SG_HIP(hipGetLastError());
-  SG_HIP(hipMemcpyAsync(h_tot, J.totals, 32, hipMemcpyDeviceToHost, s));
-  SG_HIP(hipStreamSynchronize(s));
-  if ((rc = inflate_verdicts(ctx, mem, T->bgzf_meta, "sg_train_feed_bgzf")) != SG_OK) return rc;
-  auto record_error = [&](uint64_t key) {
-    return ctx->fail(SG_ERR_INVALID, "sg_train_feed_bgzf: BAM record at decompressed offset " + std::to_string(T->bam_stream_off + (key >> 8)) + ": " +
-                                         bam_verdict((uint32_t)(key & 0xFF)));
-  };
-  if (h_tot[3] != ~0ull) return record_error(h_tot[3]);
-  const uint64_t n_rec = h_tot[0], tail = h_tot[2];
+  if ((rc = bam_stream_records(ctx, T->in, "sg_train_feed_bgzf", s, T->copy_stream, &J)) != SG_OK) return rc;
+  const uint64_t n_rec = J.n_rec;
   uint64_t text_bytes = 0;
   if (n_rec) {
-    SG_ENSURE(T->rec, n_rec * 8 + 64);
     SG_ENSURE(T->line_len, n_rec * 4 + 64);
     SG_ENSURE(T->line_off, n_rec * 8 + 64);
-    SG_ENSURE(T->bam_scan, (size_t)(sg::scan_blocks((uint32_t)n_rec) + 1) * 8 + 64);
-    J.scan_bsum = T->bam_scan.as<uint64_t>();
-    J.rec = T->rec.as<uint64_t>();
-    J.n_rec = n_rec;
     J.line_len = T->line_len.as<uint32_t>();
     J.line_off = T->line_off.as<uint64_t>();
-    sg::launch_bam_starts(J, s);
     sg::launch_bam_measure(J, s);
     sg::launch_scan_u32(J.line_len, (uint32_t)n_rec, J.scan_bsum, J.line_off, J.totals + 1, s);
-    SG_HIP(hipGetLastError());
-    SG_HIP(hipMemcpyAsync(h_tot, J.totals, 32, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
-    if (h_tot[3] != ~0ull) return record_error(h_tot[3]);
+    uint64_t h_tot[4];
+    if ((rc = sg_read_back(ctx, h_tot, J.totals, 32)) != SG_OK) return rc;
+    if (h_tot[3] != ~0ull) return bam_stream_record_error(ctx, T->in, "sg_train_feed_bgzf", h_tot[3]);
     text_bytes = h_tot[1];
   }
   if (text_bytes) {
@@ -725,17 +770,7 @@ int sg_train_feed_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes) {
     sg::launch_bam_render(J, s);
     SG_HIP(hipGetLastError());
   }
-  // the partial record behind the last whole one goes to the front of the other stream buffer
-  const uint64_t left = L - tail;
-  DevBuf& N = T->stream[T->scur ^ 1];
-  SG_ENSURE(N, left + 64);
-  if (left) SG_HIP(hipMemcpyAsync(N.p, S.as<uint8_t>() + tail, left, hipMemcpyDeviceToDevice, s));
-  T->scur ^= 1;
-  T->bam_carry = left;
-  T->bam_stream_off += tail;
-  T->bam_file_off += bytes;
-  T->bam_records += n_rec;
-  T->bam_inflated += total;
+  if ((rc = bam_stream_advance(ctx, T->in, s)) != SG_OK) return rc;
   if (text_bytes) {
     SG_HIP(hipStreamSynchronize(s));
     T->bam_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -749,8 +784,8 @@ int sg_train_bam_info(sg_ctx* ctx, uint64_t* records, uint64_t* inflated_bytes, 
   if (!ctx) return SG_ERR_INVALID;
   sg_train_session* T = ctx->train;
   if (!T || !T->bam) return ctx->fail(SG_ERR_INVALID, "sg_train_bam_info: no BAM input in this session");
-  if (records) *records = T->bam_records;
-  if (inflated_bytes) *inflated_bytes = T->bam_inflated;
+  if (records) *records = T->in.records;
+  if (inflated_bytes) *inflated_bytes = T->in.inflated;
   if (seconds) *seconds = T->bam_seconds;
   return SG_OK;
 }
