@@ -1,8 +1,9 @@
 // host/common.h -- small shared helpers of the C++ host side (string handling with the reference's
-// exact semantics, host Philox for the two host-side draw kinds, error type).
+// exact semantics, host Philox for the two host-side draw kinds, error type and the entry points' error wrapper).
 #pragma once
 #include <chrono>
 #include <cstdint>
+#include <cstring>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -16,6 +17,17 @@ struct Error : std::runtime_error {
   int exit_code;
   Error(const std::string& m, int code = 1) : std::runtime_error(m), exit_code(code) {}
 };
+
+// What every entry point of the host library does with an error: its text into `err`, its exit code returned (0: fn ran through).
+template <class Fn>
+int guarded(char* err, size_t err_len, Fn fn) {
+  auto say = [&](const char* m) {
+    if (err && err_len) { strncpy(err, m, err_len - 1); err[err_len - 1] = '\0'; }
+  };
+  try { fn(); return 0; }
+  catch (const Error& e) { say(e.what()); return e.exit_code ? e.exit_code : 1; }
+  catch (const std::exception& e) { say(e.what()); return 1; }
+}
 
 struct Timed {  // adds the time a scope took to one of the stats' timers, however the scope is left
   double& d;

@@ -1,6 +1,6 @@
 // host/eval.cpp -- see eval.h.  The host keeps what happens once per file -- options, the header, the @SQ names and the
 // map between the two files' refIDs, the text of eval.tsv -- and streams both files through the GPU in batches of whole BGZF
-// members while a reader thread fills the next batch (BamReader, host/bam_reader.h).
+// members while a reader thread fills the next batch (BatchReader and stream_batches, host/input_stream.h).
 #include "eval.h"
 
 #include <chrono>
@@ -11,12 +11,13 @@
 #include <map>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../../include/simuscop_amd.h"
 #include "bam_reader.h"
 #include "common.h"
+#include "engine.h"
+#include "input_stream.h"
 
 namespace simu {
 namespace {
@@ -26,14 +27,6 @@ double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::
 
 constexpr uint32_t kCategories = 8, kClasses = 3, kMapqs = 256;
 const char* const kClassName[kClasses] = {"plain", "edited", "unmapped"};
-
-struct Engine {
-  sg_ctx* ctx = nullptr;
-  ~Engine() { if (ctx) { sg_eval_end(ctx); sg_destroy(ctx); } }
-  void check(int rc, const char* what) const {
-    if (rc != SG_OK) throw Error(std::string("GPU engine error in ") + what + ": " + sg_last_error(ctx));
-  }
-};
 
 // Refused before a device is touched: a file that cannot be opened, or whose first bytes are no BGZF member.
 void need_bgzf(const std::string& path) {
@@ -51,13 +44,9 @@ void need_bgzf(const std::string& path) {
 // One file through `feed` (sg_eval_truth_bgzf / sg_eval_test_bgzf), `start` called with its header in front of the first batch.
 template <class Start, class Feed>
 uint64_t stream_file(const Engine& eng, const std::string& path, int threads, Start start, Feed feed) {
-  BamReader rd(eng.ctx, path, threads);
-  if (rd.fd < 0) throw Error("Error: " + path + " is not a regular file (the header is read first, then the file from its start)", 1);
-  if (rd.size >= 28) {
-    rd.last28.resize(28);
-    if (pread(rd.fd, &rd.last28[0], 28, (off_t)(rd.size - 28)) != 28) rd.last28.clear();
-  }
-  if (!rd.eof_marker()) std::cerr << "[W::bam_hdr_read] EOF marker is absent. The input is probably truncated" << std::endl;
+  BatchReader rd(eng.ctx, path, "BAM", threads, BatchReader::Members);
+  if (!rd.regular()) throw Error("Error: " + path + " is not a regular file (the header is read first, then the file from its start)", 1);
+  if (!rd.peek_eof_marker()) std::cerr << "[W::bam_hdr_read] EOF marker is absent. The input is probably truncated" << std::endl;
   BamHeader H;
   std::vector<std::string> replay;
   bam_prepare(eng.ctx, rd, H, replay);
@@ -67,20 +56,7 @@ uint64_t stream_file(const Engine& eng, const std::string& path, int threads, St
     if (rc != SG_OK) throw Error(std::string("Error: ") + sg_last_error(eng.ctx) + " (" + path + ")", 1);
   };
   uint64_t fed = 0;
-  int cur = 0;
-  bool more = rd.fill(cur);
-  while (more) {
-    bool next = false;
-    std::string reader_error;
-    std::thread reader([&]() { try { next = rd.fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
-    const int rc = feed(rd.buf[cur], rd.len[cur]);
-    reader.join();
-    said(rc);
-    if (!reader_error.empty()) throw Error(reader_error);
-    fed += rd.len[cur];
-    cur ^= 1;
-    more = next;
-  }
+  stream_batches(rd, [&](const char* p, uint64_t n) { said(feed(p, n)); fed += n; });
   said(feed(nullptr, 0));
   return fed;
 }
@@ -195,21 +171,11 @@ extern "C" void simu_eval_default_options(simu_eval_options* o) {
 }
 
 extern "C" int simu_eval(const simu_eval_options* opt, simu_eval_stats* stats, char* err, size_t err_len) {
-  auto set_err = [&](const std::string& m) {
-    if (err && err_len) { strncpy(err, m.c_str(), err_len - 1); err[err_len - 1] = '\0'; }
-  };
-  if (!opt) { set_err("no options"); return 1; }
-  simu_eval_stats st;
-  std::memset(&st, 0, sizeof st);
-  try {
+  return simu::guarded(err, err_len, [&]() {
+    if (!opt) throw simu::Error("no options");
+    simu_eval_stats st;
+    std::memset(&st, 0, sizeof st);
     simu::run(*opt, st);
     if (stats) *stats = st;
-    return 0;
-  } catch (const simu::Error& e) {
-    set_err(e.what());
-    return e.exit_code ? e.exit_code : 1;
-  } catch (const std::exception& e) {
-    set_err(e.what());
-    return 1;
-  }
+  });
 }

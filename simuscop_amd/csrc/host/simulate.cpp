@@ -879,22 +879,12 @@ extern "C" int simu_run(const char* config_path, const simu_options* opt, simu_s
   simu_options o;
   if (opt) o = *opt; else simu_default_options(&o);
   if (o.shard_world < 1) o.shard_world = 1;
-  auto set_err = [&](const std::string& m) {
-    if (err && err_len) { strncpy(err, m.c_str(), err_len - 1); err[err_len - 1] = '\0'; }
-  };
-  try {
+  return simu::guarded(err, err_len, [&]() {
     std::unique_ptr<simu::Driver> d(new simu::Driver());
     d->opt = o;
     d->run(config_path ? config_path : "");
     if (stats) *stats = d->st;
-    return 0;
-  } catch (const simu::Error& e) {
-    set_err(e.what());
-    return e.exit_code == 0 ? 1 : e.exit_code;
-  } catch (const std::exception& e) {
-    set_err(e.what());
-    return 1;
-  }
+  });
 }
 
 extern "C" int simu_selftest_haplotypes(const char* config_path, uint64_t seed, char* err, size_t err_len) {
@@ -958,19 +948,13 @@ extern "C" int simu_selftest_haplotypes(const char* config_path, uint64_t seed, 
 // ------------------------------------------------------------------------------------------------
 struct simu_session { simu::Driver d; };
 
-static int session_guard(char* err, size_t err_len, const std::function<void()>& fn) {
-  try { fn(); return 0; }
-  catch (const simu::Error& e) { if (err && err_len) { strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; } return e.exit_code ? e.exit_code : 1; }
-  catch (const std::exception& e) { if (err && err_len) { strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; } return 1; }
-}
-
 extern "C" int simu_open(const char* config_path, const simu_options* opt, simu_session** out, char* err, size_t err_len) {
   if (!out) return 1;
   *out = nullptr;
   std::unique_ptr<simu_session> s(new simu_session());
   if (opt) s->d.opt = *opt; else simu_default_options(&s->d.opt);
   if (s->d.opt.shard_world < 1) s->d.opt.shard_world = 1;
-  int rc = session_guard(err, err_len, [&]() { s->d.open(config_path ? config_path : ""); });
+  int rc = simu::guarded(err, err_len, [&]() { s->d.open(config_path ? config_path : ""); });
   if (rc == 0) *out = s.release();
   return rc;
 }
@@ -981,7 +965,7 @@ extern "C" int simu_chromosome_count(simu_session* s) { return (int)s->d.genome.
 // Sum over this session's chromosomes of the GC-weighted length of population `popu`
 // (Genome::setReadCounts' WL, Genome.cpp:787-797).  Runs pass 1 (haplotypes + GPU GC scan) on first use.
 extern "C" int simu_weighted_length(simu_session* s, int popu, double* wl, char* err, size_t err_len) {
-  return session_guard(err, err_len, [&]() {
+  return simu::guarded(err, err_len, [&]() {
     simu::Driver& d = s->d;
     const std::string& p = d.cfg.popu_names.at(popu);
     double WL = 0;
@@ -996,18 +980,18 @@ extern "C" int simu_weighted_length(simu_session* s, int popu, double* wl, char*
   });
 }
 extern "C" int simu_set_reads(simu_session* s, int popu, int64_t reads, char* err, size_t err_len) {
-  return session_guard(err, err_len, [&]() { s->d.set_read_counts(s->d.cfg.popu_names.at(popu), (long)reads); });
+  return simu::guarded(err, err_len, [&]() { s->d.set_read_counts(s->d.cfg.popu_names.at(popu), (long)reads); });
 }
 // Upload the chromosome's haplotype chains and hand its sampling plan to the engine.  `has_work`
 // is 0 when this shard has nothing to sample there.
 extern "C" int simu_prepare_batch(simu_session* s, int popu, int chr, int* has_work, char* err, size_t err_len) {
-  return session_guard(err, err_len, [&]() {
+  return simu::guarded(err, err_len, [&]() {
     bool w = s->d.prepare_batch(s->d.cfg.popu_names.at(popu), s->d.genome.chromosomes.at(chr));
     if (has_work) *has_work = w ? 1 : 0;
   });
 }
 extern "C" int simu_variant_table(simu_session* s, void* rows, uint64_t cap, uint64_t* n, char* err, size_t err_len) {
-  return session_guard(err, err_len, [&]() {
+  return simu::guarded(err, err_len, [&]() {
     if (!s || !n) throw simu::Error("simu_variant_table: no session");
     if (!s->d.opt.truth_variants) throw simu::Error("simu_variant_table: the session was not opened with truth_variants");
     const std::vector<sg_variant> a = s->d.truth->variant_table().abi();

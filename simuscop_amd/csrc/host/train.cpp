@@ -1,16 +1,12 @@
 // host/train.cpp -- see train.h.  The host keeps what the reference's seqToProfile does once per run -- options, the VCF,
 // the BED file, the arithmetic on the finished count matrices (a few hundred thousand numbers) and the file format -- and
 // streams the reads through the GPU: the reference to HBM (Fasta::open_on_device), the SAM text in pinned chunks of whole
-// lines while a reader thread fills the next one (sg_train_feed).
+// lines while a reader thread fills the next one (sg_train_feed; BatchReader and stream_batches, host/input_stream.h).
 #include "train.h"
-
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,17 +15,16 @@
 #include <iostream>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <sstream>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../../include/simuscop_amd.h"
 #include "common.h"
 #include "bam_reader.h"
+#include "engine.h"
 #include "fasta.h"
-#include "reader_pool.h"
+#include "input_stream.h"
 
 namespace simu {
 namespace {
@@ -40,15 +35,6 @@ double since(Clock::time_point t) { return std::chrono::duration<double>(Clock::
 constexpr double kZeroFinal = 2.2204e-16;   // lib/mydefine/MyDefine.cpp:20
 constexpr uint32_t kWindow = 1000;          // Segment::fragSize
 constexpr uint32_t kIsizeCols = 1u << 20, kIndelCols = 1u << 16;
-constexpr uint64_t kChunk = 64ull << 20;
-
-struct Engine {
-  sg_ctx* ctx = nullptr;
-  ~Engine() { if (ctx) sg_destroy(ctx); }
-  void check(int rc, const char* what) const {
-    if (rc != SG_OK) throw Error(std::string("GPU engine error in ") + what + ": " + sg_last_error(ctx));
-  }
-};
 
 // ---- lib/vcfparser/vcfparser.cpp:26-106 ----
 struct KnownVariants {
@@ -183,32 +169,17 @@ std::map<std::string, std::vector<Piece>> load_targets(const std::string& path, 
 }
 
 // ---- where the lines come from: a file, standard input, or `samtools view` as the reference runs it ----
-struct LineSource {
-  FILE* fp = nullptr;
-  bool piped = false;
-  std::string what;
-  ~LineSource() { close(); }
-  void close() {
-    if (fp && fp != stdin) { if (piped) pclose(fp); else fclose(fp); }
-    fp = nullptr;
-  }
-  void open(const simu_train_options& o) {
-    close();
-    const std::string sam = o.sam ? o.sam : "";
-    if (!sam.empty()) {
-      what = sam;
-      if (sam == "-") fp = stdin;
-      else if (!(fp = fopen(sam.c_str(), "r"))) throw Error("cannot open SAM file " + sam, -1);
-      return;
-    }
-    std::string samtools = o.samtools ? o.samtools : "";
-    if (samtools.empty()) samtools = "samtools";
-    what = o.bam ? o.bam : "";
-    const std::string cmd = samtools + " view -F 0xD04 -q 20 " + what;   // Profile.cpp:1448
-    piped = true;
-    if (!(fp = popen(cmd.c_str(), "r"))) throw Error("cannot open BAM file " + what, -1);
-  }
-};
+std::unique_ptr<BatchReader> open_lines(sg_ctx* ctx, const simu_train_options& o) {
+  const std::string sam = o.sam ? o.sam : "";
+  if (!sam.empty()) return std::unique_ptr<BatchReader>(new BatchReader(ctx, sam, "SAM", o.threads, BatchReader::Lines));
+  std::string samtools = o.samtools ? o.samtools : "";
+  if (samtools.empty()) samtools = "samtools";
+  const std::string bam = o.bam ? o.bam : "";
+  const std::string cmd = samtools + " view -F 0xD04 -q 20 " + bam;   // Profile.cpp:1448
+  FILE* fp = popen(cmd.c_str(), "r");
+  if (!fp) throw Error("cannot open BAM file " + bam, -1);
+  return std::unique_ptr<BatchReader>(new BatchReader(ctx, fp, pclose, bam, o.threads, BatchReader::Lines));
+}
 
 // CIGAR of a line when it is a single nM (Profile::setReadLength, Profile.cpp:155-163), else 0
 int single_match_length(const char* p, const char* le) {
@@ -223,68 +194,6 @@ int single_match_length(const char* p, const char* le) {
   if (n >= 1 && i == n - 1 && p[i] == 'M') return atoi(std::string(p, e).c_str());
   return 0;
 }
-
-// Pinned chunks of whole lines, read ahead while the device works on the chunk before.  A regular file is read by a pool of
-// threads (pread of 4 MB slices: one reader took text at 10 GB/s, a fifth of what the link and the kernels take); a pipe
-// or standard input by the one thread there can be.
-struct ChunkReader {
-  sg_ctx* ctx;
-  FILE* fp;
-  int fd = -1;                // >= 0: a regular file, read with pread from `pos`
-  uint64_t pos = 0, size = 0;
-  std::unique_ptr<ReaderPool> pool;
-  char* buf[2] = {nullptr, nullptr};
-  uint64_t len[2] = {0, 0};
-  std::string carry;          // the unfinished line behind a chunk's last line break
-  bool eof = false;
-  bool whole_lines = true;    // false: chunks are cut wherever they end (the VCF route: the device carries the partial line)
-  ChunkReader(sg_ctx* c, FILE* f, int threads) : ctx(c), fp(f) {
-    struct stat sb;
-    if (f != stdin && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
-      fd = fileno(f);
-      size = (uint64_t)sb.st_size;
-      pool.reset(new ReaderPool(std::min(16, std::max(1, threads))));
-    }
-    for (int i = 0; i < 2; i++) {
-      void* p = nullptr;
-      if (sg_host_alloc(ctx, kChunk + 16, &p) != SG_OK) throw Error(std::string("GPU engine error in sg_host_alloc: ") + sg_last_error(ctx));
-      buf[i] = (char*)p;
-    }
-  }
-  ~ChunkReader() { for (char* b : buf) if (b) sg_host_free(ctx, b); }
-  // fills buf[i] with whole lines; false when nothing is left
-  bool fill(int i) {
-    if (eof && carry.empty()) { len[i] = 0; return false; }
-    uint64_t have = carry.size();
-    if (have > kChunk) throw Error("a line of the SAM text is longer than 64 MB");
-    memcpy(buf[i], carry.data(), have);
-    carry.clear();
-    if (fd >= 0) {
-      const uint64_t n = std::min<uint64_t>(kChunk - have, size - pos);
-      if (n) parallel_pread(*pool, fd, (uint8_t*)buf[i] + have, pos, n);
-      have += n;
-      pos += n;
-      if (pos >= size) eof = true;
-    } else {
-      while (!eof && have < kChunk) {
-        const size_t got = fread(buf[i] + have, 1, kChunk - have, fp);
-        if (got == 0) { eof = true; break; }
-        have += got;
-      }
-    }
-    if (!eof && whole_lines) {   // cut behind the last line break
-      uint64_t cut = have;
-      while (cut > 0 && buf[i][cut - 1] != '\n') cut--;
-      if (cut == 0) throw Error("a line of the SAM text is longer than 64 MB");
-      carry.assign(buf[i] + cut, have - cut);
-      have = cut;
-    }
-    len[i] = have;
-    return have > 0;
-  }
-};
-
-constexpr uint64_t kVcfBatch = 8ull << 20;    // compressed bytes per batch of a BGZF VCF (text: several times more per byte than BAM records)
 
 int bam_record_single_match(const uint8_t* r, uint32_t bs) {
   const int32_t ref = (int32_t)le32(r + 4), pos = (int32_t)le32(r + 8), lseq = (int32_t)le32(r + 20);
@@ -323,7 +232,7 @@ int bam_record_single_match(const uint8_t* r, uint32_t bs) {
 }
 
 // The device route of the VCF: the file's text (plain: pinned chunks cut anywhere; BGZF: batches of whole members) goes
-// through sg_vcf_feed / sg_vcf_feed_bgzf while a reader thread fills the next chunk.  The fragments the device leaves
+// through sg_vcf_feed / sg_vcf_feed_bgzf while a reader thread fills the next chunk (stream_batches).  The fragments the device leaves
 // undecided go through vcf_fragment here and are merged back by fragment number, so every list keeps the file's order.
 void load_vcf_device(sg_ctx* ctx, const std::string& path, bool bgzf, const std::map<std::string, uint32_t>& row_of, KnownVariants& kv, bool quiet, int threads, simu_train_stats& st) {
   auto said = [&](int rc, const char* where) {
@@ -358,49 +267,17 @@ void load_vcf_device(sg_ctx* ctx, const std::string& path, bool bgzf, const std:
       if (hv.del_pos.size() > before[2]) h_num[2].push_back(f.number);
     }
   };
-  if (bgzf) {
-    BamReader rd(ctx, path, threads, "VCF", kVcfBatch);
-    if (rd.fd >= 0) {
-      if (rd.size >= 28) {
-        rd.last28.resize(28);
-        if (pread(rd.fd, &rd.last28[0], 28, (off_t)(rd.size - 28)) != 28) rd.last28.clear();
-      }
-      if (!rd.eof_marker()) std::cerr << "Warning: no BGZF EOF marker at the end of " << path << ". The input is probably truncated" << std::endl;
-    }
-    int cur = 0;
-    bool more = rd.fill(cur);
-    while (more) {
-      bool next = false;
-      std::string reader_error;
-      std::thread reader([&]() { try { next = rd.fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
-      const int rc = sg_vcf_feed_bgzf(ctx, rd.buf[cur], rd.len[cur]);
-      reader.join();
-      said(rc, "sg_vcf_feed_bgzf");
-      if (!reader_error.empty()) throw Error(reader_error);
+  {
+    FILE* fp = fopen(path.c_str(), "rb");   // (the two forms have always worded this differently)
+    if (!fp) throw Error((bgzf ? "cannot open VCF file " : "Error: cannot open VCF file ") + path, -1);
+    BatchReader rd(ctx, fp, fclose, path, threads, bgzf ? BatchReader::Members : BatchReader::Anywhere, bgzf ? kVcfBatch + kMaxMember : kChunk);
+    if (bgzf && rd.regular() && !rd.peek_eof_marker())
+      std::cerr << "Warning: no BGZF EOF marker at the end of " << path << ". The input is probably truncated" << std::endl;
+    stream_batches(rd, [&](const char* p, uint64_t n) {
+      if (bgzf) said(sg_vcf_feed_bgzf(ctx, p, n), "sg_vcf_feed_bgzf");
+      else said(sg_vcf_feed(ctx, p, n), "sg_vcf_feed");
       resolve();
-      cur ^= 1;
-      more = next;
-    }
-  } else {
-    FILE* fp = fopen(path.c_str(), "rb");
-    if (!fp) throw Error("Error: cannot open VCF file " + path, -1);
-    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
-    ChunkReader rd(ctx, fp, threads);
-    rd.whole_lines = false;
-    int cur = 0;
-    bool more = rd.fill(cur);
-    while (more) {
-      bool next = false;
-      std::string reader_error;
-      std::thread reader([&]() { try { next = rd.fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
-      const int rc = sg_vcf_feed(ctx, rd.buf[cur], rd.len[cur]);
-      reader.join();
-      said(rc, "sg_vcf_feed");
-      if (!reader_error.empty()) throw Error(reader_error);
-      resolve();
-      cur ^= 1;
-      more = next;
-    }
+    });
   }
   sg_vcf_counts C;
   said(sg_vcf_finish(ctx, &C), "sg_vcf_finish");
@@ -685,34 +562,20 @@ void run(const simu_train_options& o, simu_train_stats& st) {
   tfirst[key_of_row.size()] = tspos.size();
   // ---- Profile::init (Profile.cpp:172-218): the read length is the first single-nM CIGAR of the text ----
   const bool decode_bam = o.decode_bam != 0;
-  LineSource src;
-  std::unique_ptr<ChunkReader> rd;
-  std::unique_ptr<BamReader> brd;
+  std::unique_ptr<BatchReader> rd;   // the BAM's members (--decode-bam), else lines of SAM text
   BamHeader bam_header;
   std::vector<std::string> replay;   // (standard input: the batches the header and the read length took)
-  int cur = 0;
-  bool have = false;
   int read_length = 0;
   if (decode_bam) {
-    brd.reset(new BamReader(eng.ctx, o.bam ? o.bam : "", o.threads));
-    src.what = brd->what;
-    if (brd->fd >= 0) {   // a file shows its end now; a pipe once it is read
-      if (brd->size >= 28) {
-        brd->last28.resize(28);
-        if (pread(brd->fd, &brd->last28[0], 28, (off_t)(brd->size - 28)) != 28) brd->last28.clear();
-      }
-      if (!brd->eof_marker()) std::cerr << "[W::bam_hdr_read] EOF marker is absent. The input is probably truncated" << std::endl;
-    }
-    bam_prepare(eng.ctx, *brd, bam_header, replay, bam_record_single_match, &read_length);
-    if (brd->fd >= 0) brd->rewind();
+    rd.reset(new BatchReader(eng.ctx, o.bam ? o.bam : "", "BAM", o.threads, BatchReader::Members));
+    if (rd->regular() && !rd->peek_eof_marker())   // a file shows its end now; a pipe once it is read
+      std::cerr << "[W::bam_hdr_read] EOF marker is absent. The input is probably truncated" << std::endl;
+    bam_prepare(eng.ctx, *rd, bam_header, replay, bam_record_single_match, &read_length);
+    if (rd->regular()) rd->rewind();
   } else {
-    src.open(o);
-    rd.reset(new ChunkReader(eng.ctx, src.fp, o.threads));
-    have = rd->fill(cur);
-  }
-  if (!decode_bam) {
-    const char* p = rd->buf[cur];
-    const char* end = p + rd->len[cur];
+    rd = open_lines(eng.ctx, o);
+    const char* p = rd->data(0);
+    const char* end = p + (rd->first() ? rd->len[0] : 0);
     while (p < end && !read_length) {
       const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
       const char* le = nl ? nl : end;
@@ -720,7 +583,8 @@ void run(const simu_train_options& o, simu_train_stats& st) {
       p = nl ? nl + 1 : end;
     }
   }
-  if (read_length <= 0) throw Error("Error: no read with a single match in its CIGAR among the first lines of " + src.what);
+  const std::string reads_label = rd->what;
+  if (read_length <= 0) throw Error("Error: no read with a single match in its CIGAR among the first lines of " + reads_label);
   Model M;
   M.bases = "ACTG";   // (Config.cpp: the default of "bases"; seqToProfile has no option for it)
   M.kmer = o.kmer; M.bins = std::min(o.bins, read_length); M.read_length = read_length;
@@ -746,6 +610,7 @@ void run(const simu_train_options& o, simu_train_stats& st) {
     if (rc == SG_ERR_INVALID && m.find("malformed read") != std::string::npos) throw Error(m, 1);
     throw Error(std::string("GPU engine error in ") + where + ": " + m);
   };
+  auto not_capped = [&]() { return !sg_train_capped(eng.ctx); };   // (at the cap the reference leaves its loop: the rest of the input is not read)
   if (decode_bam) {
     std::vector<const char*> names;
     for (const std::string& n : bam_header.names) names.push_back(n.c_str());
@@ -756,36 +621,14 @@ void run(const simu_train_options& o, simu_train_stats& st) {
       st.bam_bytes += b.size();
     }
     replay.clear();
-    bool more = !sg_train_capped(eng.ctx) && brd->fill(cur);
-    while (more) {
-      bool next = false;
-      std::string reader_error;
-      std::thread reader([&]() { try { next = brd->fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
-      const int rc = sg_train_feed_bgzf(eng.ctx, brd->buf[cur], brd->len[cur]);
-      reader.join();
-      engine_said(rc, "sg_train_feed_bgzf");
-      if (!reader_error.empty()) throw Error(reader_error);
-      st.bam_bytes += brd->len[cur];
-      cur ^= 1;
-      more = next && !sg_train_capped(eng.ctx);
-    }
-    if (!sg_train_capped(eng.ctx)) engine_said(sg_train_feed_bgzf(eng.ctx, nullptr, 0), "sg_train_feed_bgzf");
-    if (brd->fd < 0 && !brd->eof_marker() && !sg_train_capped(eng.ctx))
+    if (not_capped())
+      stream_batches(*rd, [&](const char* p, uint64_t n) { engine_said(sg_train_feed_bgzf(eng.ctx, p, n), "sg_train_feed_bgzf"); st.bam_bytes += n; }, not_capped);
+    if (not_capped()) engine_said(sg_train_feed_bgzf(eng.ctx, nullptr, 0), "sg_train_feed_bgzf");
+    if (!rd->regular() && !rd->eof_marker() && not_capped())
       std::cerr << "[W::bam_hdr_read] EOF marker is absent. The input is probably truncated" << std::endl;
     eng.check(sg_train_bam_info(eng.ctx, &st.bam_records, nullptr, &st.t_inflate), "sg_train_bam_info");
-  }
-  while (have) {
-    // the next chunk is read while the device works on this one
-    bool more = false;
-    std::string reader_error;
-    std::thread reader([&]() { try { more = rd->fill(cur ^ 1); } catch (const std::exception& e) { reader_error = e.what(); } });
-    const int rc = sg_train_feed(eng.ctx, rd->buf[cur], rd->len[cur]);
-    reader.join();
-    engine_said(rc, "sg_train_feed");
-    if (!reader_error.empty()) throw Error(reader_error);
-    st.sam_bytes += rd->len[cur];
-    cur ^= 1;
-    have = more && !sg_train_capped(eng.ctx);   // (at the cap the reference leaves its loop: the rest of the input is not read)
+  } else {
+    stream_batches(*rd, [&](const char* p, uint64_t n) { engine_said(sg_train_feed(eng.ctx, p, n), "sg_train_feed"); st.sam_bytes += n; }, not_capped);
   }
   const size_t subs_n = (size_t)M.kmer_count * M.bins * 4, kmers_n = (size_t)M.bins * M.kmer_count, qual_n = (size_t)16 * M.bins * 94;
   std::vector<uint64_t> c_subs1(subs_n), c_subs2(subs_n), c_kmers(kmers_n), c_qual(qual_n), c_isize(kIsizeCols), c_ins(kIndelCols), c_del(kIndelCols);
@@ -807,8 +650,6 @@ void run(const simu_train_options& o, simu_train_stats& st) {
   }
   st.t_reads = since(t1);
   rd.reset();
-  brd.reset();
-  src.close();
   if (C.isize_overflow || C.indel_len_overflow)
     throw Error("Error: insert sizes beyond " + std::to_string(kIsizeCols) + " or CIGAR insertions / deletions beyond " + std::to_string(kIndelCols) +
                 " bases in the reads (" + std::to_string(C.isize_overflow) + " / " + std::to_string(C.indel_len_overflow) + " of them): not representable");
@@ -840,9 +681,9 @@ void run(const simu_train_options& o, simu_train_stats& st) {
   if (!output.empty()) {
     std::ofstream ofs(output.c_str());
     if (!ofs.is_open()) throw Error("Error: cannot open file to save model training results:\n" + output, -1);
-    write_profile(M, ofs, src.what, stamp);
+    write_profile(M, ofs, reads_label, stamp);
   } else {
-    write_profile(M, std::cout, src.what, stamp);
+    write_profile(M, std::cout, reads_label, stamp);
   }
   st.lines = C.lines; st.reads_counted = C.reads_counted; st.gc_rejected = C.gc_rejected; st.gc_windows = C.gc_windows;
   st.gc_pairs = n_gc; st.skipped_overhang = C.skipped_overhang; st.read_length = read_length; st.bins = M.bins;
@@ -862,21 +703,11 @@ extern "C" void simu_train_default_options(simu_train_options* o) {
 }
 
 extern "C" int simu_train(const simu_train_options* opt, simu_train_stats* stats, char* err, size_t err_len) {
-  auto set_err = [&](const std::string& m) {
-    if (err && err_len) { strncpy(err, m.c_str(), err_len - 1); err[err_len - 1] = '\0'; }
-  };
-  if (!opt) { set_err("no options"); return 1; }
-  simu_train_stats st;
-  std::memset(&st, 0, sizeof st);
-  try {
+  return simu::guarded(err, err_len, [&]() {
+    if (!opt) throw simu::Error("no options");
+    simu_train_stats st;
+    std::memset(&st, 0, sizeof st);
     simu::run(*opt, st);
     if (stats) *stats = st;
-    return 0;
-  } catch (const simu::Error& e) {
-    set_err(e.what());
-    return e.exit_code ? e.exit_code : 1;
-  } catch (const std::exception& e) {
-    set_err(e.what());
-    return 1;
-  }
+  });
 }

@@ -9,20 +9,13 @@
 #include <vector>
 
 #include "../../../include/simuscop_amd.h"
+#include "engine.h"
 #include "genome.h"
 #include "profile.h"
 #include "simulate.h"
 #include "truth_variants.h"
 
 namespace simu {
-
-struct Engine {  // RAII around sg_ctx, turns status codes into simu::Error
-  sg_ctx* ctx = nullptr;
-  ~Engine() { if (ctx) sg_destroy(ctx); }
-  void check(int rc, const char* what) {
-    if (rc != SG_OK) throw Error(std::string("GPU engine error in ") + what + ": " + sg_last_error(ctx));
-  }
-};
 
 // The reference's contigs as every truth output numbers them, made once after the inputs are loaded: the FASTA's contigs
 // in file order, each under the first token of its header line as the file writes it (`chr20` stays `chr20`, although

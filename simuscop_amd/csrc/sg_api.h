@@ -1,12 +1,15 @@
 // sg_api.h -- what the files of the C ABI share.  Internal: the ABI itself is include/simuscop_amd.h.  Who defines what:
-//   sg_memory.cpp          block and pinned-memory caches: DevBuf::ensure / release, sg_host_alloc / _free, sg_release_cached_memory
+//   sg_memory.cpp          block and pinned-memory caches: DevBuf::ensure / release, sg_grow_keep, sg_host_alloc / _free,
+//                          sg_release_cached_memory
 //   sg_api.cpp             the context, sg_load_profile / sg_load_prepared_profile, sg_plan and finish_plan, the sampling pass
 //                          (sg_sample, sg_pass_need, retire_plan), sg_result and the fetch calls, detached outputs
 //   sg_profile_tables.cpp  sg_profile_prepare and the table self-checks (host only: sg_profile_tables.h)
 //   sg_api_deflate.cpp     the BGZF sink: deflate_text, sg_compress, sg_deflate_bgzf, sg_fetch_compressed, sg_bgzf_eof
 //   sg_api_truth.cpp       truth alignments and the truth BAM: sg_pass_prelude, sg_truth_*, sg_pass_records, sg_fetch_truth
 //   sg_api_haplotypes.cpp  reference ingest and haplotype assembly: sg_reference_*, sg_build / upload_haplotypes, sg_haplotype_codes
-//   sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training, BGZF / BAM input), sg_api_depth.cpp / _variants.cpp /
+//   sg_api_bgzf.cpp        BGZF / BAM input: inflate_launch / _verdicts, the bam_stream_* calls, sg_bgzf_members, sg_inflate_bgzf
+//                          (the member walk, bgzf_walk, is sg_bgzf.h's: host only)
+//   sg_api_windows.cpp (window planner), sg_api_train.cpp (profile training: sg_train_*), sg_api_depth.cpp / _variants.cpp /
 //   _errors.cpp (true coverage, allele and error counts), sg_api_bamsort.cpp / _bamindex.cpp (the sorted truth BAM, its BAI index),
 //   sg_api_vcf.cpp (a VCF of known variants read on the device: sg_vcf_*), sg_api_eval.cpp (truthEval: sg_eval_*)
 #pragma once
@@ -298,25 +301,22 @@ struct SgSortBufs {
   uint64_t* total;
 };
 int bamsort_sort_pairs(sg_ctx* ctx, const SgSortBufs& b, uint32_t n, uint64_t k_or, uint64_t k_and);
-// BGZF input, shared by the BAM and the VCF route (sg_api_train.cpp).  bgzf_walk: the member headers of a buffer -- up to
-// `cap` whole members, *whole = the bytes they make up; a member cut by the end of the buffer ends the walk, a header
-// that is not BGZF is an error (message in *err).  inflate_launch: members of `src` (on the device) inflated to d_out +
-// member.dst, the verdicts behind the member table in `meta`.  inflate_verdicts: those verdicts, once the stream has been
-// waited for; the first member that failed names the error.
-namespace sg { struct InflateMember; }
-int bgzf_walk(const uint8_t* b, uint64_t bytes, uint64_t file_off, uint64_t cap, std::vector<sg::InflateMember>* out, uint64_t* n_out,
-              uint64_t* whole, std::string* err, uint64_t* offs = nullptr, uint32_t* bsizes = nullptr, uint32_t* isizes = nullptr);
+// BGZF input, shared by the BAM and the VCF route (sg_api_bgzf.cpp; the member walk in front of it, bgzf_walk, is in sg_bgzf.h,
+// which sg_bam.h brings in).  inflate_launch: members of `src` (on the device) inflated to d_out + member.dst, the verdicts
+// behind the member table in `meta`.  inflate_verdicts: those verdicts, once the stream has been waited for; the first
+// member that failed names the error.
 int inflate_launch(sg_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes, const std::vector<sg::InflateMember>& mem, DevBuf& meta, uint8_t* d_out,
                    hipStream_t s, hipStream_t copy);
 int inflate_verdicts(sg_ctx* ctx, const std::vector<sg::InflateMember>& mem, const DevBuf& meta, const char* who);
-// A BAM file fed as whole BGZF members in file order (sg_api_train.cpp): what sg_train_feed_bgzf and the sg_eval_*_bgzf calls
+// A BAM file fed as whole BGZF members in file order (sg_api_bgzf.cpp): what sg_train_feed_bgzf and the sg_eval_*_bgzf calls
 // share.  A call goes
 //   bam_stream_stage    the member walk and its refusals; the members start for the device on `copy` (wait for it before the
 //                       caller's buffer is let go)
 //   bam_stream_records  the members inflated into stream[scur] behind the partial record the call before left (`carry` bytes),
 //                       the header passed over (`skip`), record boundaries and the inflate / boundary refusals; `job` holds the
 //                       stream and, queued on `s`, the start of each of its n_rec whole records
-//   (the caller's own kernels over job->rec; a record they refuse: bam_stream_record_error with their error key)
+//   (the caller's own kernels over job->rec, then bam_stream_totals: job->totals on the host, a record the kernels refused
+//                       turned into the call's error by bam_stream_record_error)
 //   bam_stream_advance  the partial record behind the last whole one goes to the front of the other stream buffer
 // and bam_stream_close, at the end of the file, refuses a record left unfinished.  bam_stream_start names the references
 // (refID order; ref_names may be NULL when no kernel prints them) and where the first record starts.
@@ -339,7 +339,7 @@ int bam_stream_records(sg_ctx* ctx, SgBamStream& B, const char* who, hipStream_t
 int bam_stream_record_error(sg_ctx* ctx, const SgBamStream& B, const char* who, uint64_t key);
 int bam_stream_advance(sg_ctx* ctx, SgBamStream& B, hipStream_t s);
 int bam_stream_close(sg_ctx* ctx, const SgBamStream& B, const char* who);
-// a device buffer grown with its first keep_bytes kept (sg_api_train.cpp)
+// a device buffer grown with its first keep_bytes kept (sg_memory.cpp)
 int sg_grow_keep(sg_ctx* ctx, DevBuf& buf, size_t keep_bytes, size_t want_bytes);
 // no context, or a call in front of its output's X_begin
 inline int sg_need_begun(sg_ctx* ctx, bool on, const char* who, const char* begin) {
@@ -354,6 +354,11 @@ inline int sg_read_back(sg_ctx* ctx, void* dst, const void* src, size_t bytes) {
   SG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   SG_HIP(hipStreamSynchronize(ctx->stream));
   return SG_OK;
+}
+// J.totals on the host once the caller's kernels over a stream's records have run; a record they refused is the call's error
+static inline int bam_stream_totals(sg_ctx* ctx, const SgBamStream& B, const char* who, const sg::BamJob& J, uint64_t h_tot[4]) {
+  if (int rc = sg_read_back(ctx, h_tot, J.totals, 32)) return rc;
+  return h_tot[3] != ~0ull ? bam_stream_record_error(ctx, B, who, h_tot[3]) : SG_OK;
 }
 // [offset, offset + bytes) lies within `have` bytes.  (The sum is never formed: it wraps for a large offset.)
 inline bool sg_range_within(uint64_t offset, uint64_t bytes, uint64_t have) { return offset <= have && bytes <= have - offset; }

@@ -133,8 +133,7 @@ int sg_eval_truth_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes) {
     sg::launch_eval_truth_rows(J, E, s);
     sg::launch_scan_u32(E.name_len, (uint32_t)n_rec, J.scan_bsum, E.name_at, J.totals + 1, s);
     uint64_t h_tot[4];
-    if ((rc = sg_read_back(ctx, h_tot, J.totals, 32)) != SG_OK) return rc;
-    if (h_tot[3] != ~0ull) { S->stage = sg_eval_session::Broken; return bam_stream_record_error(ctx, S->truth, who, h_tot[3]); }
+    if ((rc = bam_stream_totals(ctx, S->truth, who, J, h_tot)) != SG_OK) { S->stage = sg_eval_session::Broken; return rc; }
     const uint64_t name_bytes = h_tot[1];
     if ((rc = sg_grow_keep(ctx, S->arena, S->arena_used, S->arena_used + name_bytes + 64)) != SG_OK) return rc;
     S->job(E);
@@ -230,8 +229,7 @@ int sg_eval_test_bgzf(sg_ctx* ctx, const void* members, uint64_t bytes) {
     sg::launch_eval_claim(J, E, s);
     sg::launch_eval_score(J, E, s);
     uint64_t h_tot[4];
-    if ((rc = sg_read_back(ctx, h_tot, J.totals, 32)) != SG_OK) return rc;
-    if (h_tot[3] != ~0ull) { S->stage = sg_eval_session::Broken; return bam_stream_record_error(ctx, S->test, who, h_tot[3]); }
+    if ((rc = bam_stream_totals(ctx, S->test, who, J, h_tot)) != SG_OK) { S->stage = sg_eval_session::Broken; return rc; }
     S->ordinal += n_rec;
   }
   if ((rc = bam_stream_advance(ctx, S->test, s)) != SG_OK) return rc;

@@ -3,20 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sg_bgzf.h"   // InflateMember, kBgzfMaxIsize, kBgzfMinMember
+
 namespace sg {
 
-constexpr uint32_t kBgzfMaxIsize = 65536;    // BGZF: at most 64 KiB of input per member (SAMv1 section 4.1)
-constexpr uint32_t kBgzfMinMember = 28;      // 18-byte header with the BC subfield, an empty final block, CRC32, ISIZE
 constexpr uint32_t kCrcLaneBytes = 1024;     // inflate_kernel: each of the 64 lanes takes the CRC of 1 KiB of a member
 constexpr uint32_t kCrcLevels = 6;           // combine tree over the 64 lanes
 constexpr uint32_t kBamSegment = 16384;      // record boundaries: bytes of the stream per speculating thread
 
-// one whole member of a batch: `src` .. `src + bytes` in the compressed batch, `isize` inflated bytes at `dst`
-struct InflateMember {
-  uint64_t src, dst;
-  uint32_t bytes, isize;
-  uint64_t file_off;   // where the member starts in the file (error messages)
-};
 // inflate verdicts, one per member (0: inflated, CRC-32 and ISIZE as the trailer says)
 enum : uint32_t { kInflOk = 0, kInflBlockType, kInflBadCode, kInflDistance, kInflOverrun, kInflTooLong, kInflIsize, kInflCrc,
                   kInflStoredLen, kInflHeader };

@@ -1,5 +1,5 @@
 // sg_memory.cpp -- the memory that outlives a context: device blocks and pinned staging buffers stay with the process and
-// serve the next request of their size.  DevBuf (sg_api.h) takes its blocks from here.
+// serve the next request of their size.  DevBuf (sg_api.h) takes its blocks from here (ensure, release, sg_grow_keep).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -166,6 +166,18 @@ int DevBuf::ensure(size_t bytes) {
 void DevBuf::release() {
   if (p) block_cache().give(p, cap, dev);
   p = nullptr; cap = 0;
+}
+
+// a device buffer grown with what it holds kept (the window arrays live across chunks, a stream's carried record and
+// an evaluation's rows across calls); declared in sg_api.h
+int sg_grow_keep(sg_ctx* ctx, DevBuf& buf, size_t keep_bytes, size_t want_bytes) {
+  if (want_bytes <= buf.cap) return SG_OK;
+  DevBuf bigger;
+  SG_ENSURE(bigger, want_bytes + want_bytes / 2);
+  if (keep_bytes) SG_HIP(hipMemcpyAsync(bigger.p, buf.p, keep_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  SG_HIP(hipStreamSynchronize(ctx->stream));
+  buf = std::move(bigger);
+  return SG_OK;
 }
 
 extern "C" {
