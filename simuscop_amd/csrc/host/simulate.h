@@ -212,6 +212,8 @@ uint64_t simu_batch_slots(simu_session* s);  // planned fragment slots of the pr
 }
 
 #include <string>
+// What a sharded run's rank puts behind the names of its FASTQ and truth BAM parts.
+inline std::string simu_shard_suffix(const simu_options& o) { return o.shard_world > 1 ? ".part" + std::to_string(o.shard_rank) : ""; }
 // The rules of the truth options, once, for whoever has to refuse a run: the text of the first one `o` breaks, or "".
 // Needs device haplotypes: an output that maps reads back to the reference reads the haplotypes' copy lists.  Cannot
 // be sharded: an output summed over a stem would come out as partial sums, one per rank.  `sharded`: more than one

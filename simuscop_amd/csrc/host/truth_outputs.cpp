@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "truth_bam.h"
 #include "truth_errors.h"
 
 namespace simu {
@@ -103,6 +104,7 @@ void TruthOutputs::begin(TruthOutput& o) {
 void TruthOutputs::begin() { for (TruthOutput& o : outs) begin(o); }
 
 void TruthOutputs::open(const std::string& dir, const std::string& stem) {
+  if (bam) bam->open(dir, stem);
   for (TruthOutput& o : outs) {
     begin(o);
     Timed timed{st.*o.timer};
@@ -115,6 +117,7 @@ void TruthOutputs::open(const std::string& dir, const std::string& stem) {
 }
 
 void TruthOutputs::piece() {
+  if (bam) bam->piece();
   for (TruthOutput& o : outs) {
     Timed timed{st.*o.timer};
     o.add();
@@ -122,6 +125,7 @@ void TruthOutputs::piece() {
 }
 
 void TruthOutputs::close() {
+  if (bam) bam->close();
   for (TruthOutput& o : outs) {
     if (!o.in_stem) continue;
     Timed timed{st.*o.timer};
@@ -138,9 +142,11 @@ void TruthOutput::put(const std::string& text) {
 }
 
 // ---- the three outputs ----
+TruthOutputs::~TruthOutputs() = default;
 TruthOutputs::TruthOutputs(Engine& eng_, const simu_options& opt_, simu_stats& st_, const ContigTable& contigs_, const Genome& genome_,
                            const Config& cfg_, const Profile& prof)
     : eng(eng_), opt(opt_), st(st_), contigs(contigs_), genome(genome_), cfg(cfg_) {
+  if (opt.truth_bam) bam.reset(new TruthBam(eng, opt, st, contigs));
   if (opt.truth_depth) {
     // the device's runs or bin sums, contig by contig in header order, put into text here
     outs.push_back(TruthOutput{".truth.depth.bedgraph", "bedGraph file to save the true depth", "the true depth's bedGraph file", &simu_stats::t_depth});

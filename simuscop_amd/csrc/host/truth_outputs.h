@@ -1,6 +1,7 @@
 // host/truth_outputs.h -- the truth outputs that are summed over a stem: --truth-depth, --truth-variants, --truth-errors.
 // Their lifecycle in the driver is here once (DESIGN.md "The summed truth outputs' lifecycle"); an output supplies only
-// what differs (TruthOutput).  --truth-bam is a stream like the FASTQ files and stays with them in the driver's sink.
+// what differs (TruthOutput).  --truth-bam is a stream, not a sum, with the same three points (truth_bam.h): it is held
+// here and driven first at each of them.
 #pragma once
 #include <cstdio>
 #include <functional>
@@ -45,11 +46,14 @@ struct TruthOutput {  // what differs between the outputs
   void put(const std::string& text);
 };
 
-// The enabled outputs in the order depth, variants, errors; every call goes over them once.
+class TruthBam;
+
+// The truth BAM, then the enabled summed outputs in the order depth, variants, errors; every call goes over them once.
 struct TruthOutputs {
   TruthOutputs(Engine& eng, const simu_options& opt, simu_stats& st, const ContigTable& contigs, const Genome& genome, const Config& cfg,
                const Profile& prof);
-  void begin();                                               // on first use (a session has no stems: its caller adds, reads and resets itself)
+  ~TruthOutputs();
+  void begin();                                               // on first use (a session has no stems: its caller adds, reads and resets itself, and makes its own sg_truth_bam calls)
   void open(const std::string& dir, const std::string& stem); // a stem starts: the file, under write_files only
   void piece();                                               // the pass just sampled
   void close();                                               // the stem ends: render, write, reset; nothing without a stem
@@ -57,6 +61,7 @@ struct TruthOutputs {
 
  private:
   void begin(TruthOutput& o);
+  std::unique_ptr<TruthBam> bam;
   std::vector<TruthOutput> outs;
   Engine& eng;
   const simu_options& opt;
