@@ -41,8 +41,12 @@ int finish_plan(sg_ctx* ctx, uint64_t nw, uint32_t n_segs, uint32_t n_slots, uin
   const uint32_t nm = paired ? 2 : 1;
   SG_ENSURE(ctx->prefix, plen + 16);
   SG_ENSURE(ctx->pairs, ((size_t)n_slots + 1) * sizeof(sg::PairRec));
-  SG_ENSURE(ctx->win_actual, (nw + 1) * 4);
   SG_ENSURE(ctx->win_namebase, (nw + 1) * 4);
+  SG_ENSURE(ctx->win_slot, (nw + 1) * 4);
+  SG_ENSURE(ctx->win_flag, (nw + 1) * 4);
+  SG_ENSURE(ctx->win_rows, (nw + 1) * sizeof(sg::WinRow));
+  SG_ENSURE(ctx->blk_win, ((size_t)(n_slots + 255) / 256 + 1) * 4);
+  SG_ENSURE(ctx->seg_flags, ((size_t)n_segs + 1) * 2 * 4);   // seg_flag, seg_lost
   SG_ENSURE(ctx->events, ((size_t)nm * n_slots + 1) * 4 * SG_MAX_EVENTS);
   SG_ENSURE(ctx->recoff, ((size_t)nm * n_slots + 1) * 4);
   SG_ENSURE(ctx->meta, ((size_t)nm * n_slots + 1) * 48);
@@ -67,8 +71,13 @@ int finish_plan(sg_ctx* ctx, uint64_t nw, uint32_t n_segs, uint32_t n_slots, uin
   for (int i = 0; i < 4; i++) B.prefix_w[i] = 0;
   for (size_t i = 0; i < plen && i < 16; i++) B.prefix_w[i / 4] |= (uint32_t)(uint8_t)name_prefix[i] << (8 * (i % 4));
   B.pairs = ctx->pairs.as<sg::PairRec>();
-  B.win_actual = ctx->win_actual.as<uint32_t>();
   B.win_namebase = ctx->win_namebase.as<uint32_t>();
+  B.win_slot = ctx->win_slot.as<uint32_t>();
+  B.win_flag = ctx->win_flag.as<uint32_t>();
+  B.win_rows = ctx->win_rows.as<sg::WinRow>();
+  B.blk_win = ctx->blk_win.as<uint32_t>();
+  B.seg_flag = ctx->seg_flags.as<uint32_t>();
+  B.seg_lost = B.seg_flag + n_segs + 1;
   B.events = ctx->events.as<uint32_t>();
   B.recloc = ctx->recoff.as<uint32_t>();
   B.blkbase = ctx->bsum.as<uint64_t>();
@@ -76,6 +85,11 @@ int finish_plan(sg_ctx* ctx, uint64_t nw, uint32_t n_segs, uint32_t n_slots, uin
   B.meta = ctx->meta.as<uint4>();
   B.totals = ctx->totals.as<uint64_t>();
   B.slowq_count = (uint32_t*)(B.totals + 4);
+  // the batch's own tables (slot -> window, edge windows, flagged segments), from the windows now on the device and the
+  // loaded profile: made once here, read by every pass over the batch
+  SG_HIP(hipMemsetAsync(B.seg_flag, 0, ((size_t)n_segs + 1) * 2 * 4, ctx->stream));
+  sg::launch_batch_map(ctx->P, B, ctx->stream);
+  SG_HIP(hipGetLastError());
   ctx->pass = sg_ctx::Pass(sg_ctx::Pass::Planned);
   return SG_OK;
 }
@@ -142,13 +156,14 @@ static int run_pass(sg_ctx* ctx) {
   if (const char* fd = getenv("SG_FDIAG")) B.diag = (uint32_t)atoi(fd);
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
-  if (!B.n_windows) SG_HIP(hipMemsetAsync(B.totals, 0, sg::kTotalsBytes, s));  // (otherwise plan_kernel clears them)
+  if (!B.n_windows) SG_HIP(hipMemsetAsync(B.totals, 0, sg::kTotalsBytes, s));  // (otherwise edge_kernel clears them)
+  // the six intervals of SG_K_NAMES: "plan" is edge_kernel, "namebase" is empty (the numbers are made in the other two),
+  // "indel" is fragment_kernel
   if (prof) SG_HIP(hipEventRecord(ctx->evs[0], s));
-  sg::launch_plan(ctx->P, B, s);
+  sg::launch_edge(ctx->P, B, s);
   if (prof) SG_HIP(hipEventRecord(ctx->evs[1], s));
-  sg::launch_namebase(B, s);
   if (prof) SG_HIP(hipEventRecord(ctx->evs[2], s));
-  sg::launch_indel(ctx->P, B, s);
+  sg::launch_fragment(ctx->P, B, s);
   if (prof) SG_HIP(hipEventRecord(ctx->evs[3], s));
   sg::launch_scan(B, s);
   if (prof) SG_HIP(hipEventRecord(ctx->evs[4], s));

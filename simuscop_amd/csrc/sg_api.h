@@ -68,7 +68,7 @@ struct sg_ctx {
   sg::DevProfile P{};
   sg::DevBatch B{};
   OutputSet out;
-  DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_actual, win_namebase, events, recoff, meta, totals, bsum,
+  DevBuf tab, chains, chains2, chain_meta, windows, segmeta, prefix, pairs, win_namebase, win_slot, win_flag, win_rows, blk_win, seg_flags, events, recoff, meta, totals, bsum,
       slowq, ref_raw, ref_codes, ref_meta, hap_work, gz_work,
       infl_src, infl_meta, infl_out, infl_crc,   // sg_inflate_bgzf (infl_crc also serves the training session's BAM input)
       defl_src, defl_out;                        // sg_deflate_bgzf: the caller's text and its members

@@ -21,13 +21,26 @@ constexpr int kBaseRounds = 7;
 
 enum : uint32_t { KIND_HAP = 1, KIND_GC = 2, KIND_PLAN = 3, KIND_INDEL = 4, KIND_AUX = 5, KIND_BASE = 6 };
 
-// One planned fragment (16 B).  Written by plan_kernel, read by the indel and emit kernels.
-struct PairRec {   // 32 bytes per planned fragment: everything indel_kernel needs of the fragment's window but its name base
+// One planned fragment: what fragment_kernel needs of it but its name base.  A fragment of a safe window lives in its
+// lane's registers only; edge_kernel leaves the fragments of edge windows in DevBatch::pairs.
+struct PairRec {
   uint32_t win;     // window index in the batch
   uint32_t namepos; // fragment start inside its segment: (window.spos + draw) % segment size (Segment.cpp:780)
   uint32_t fl;      // bits 0..30 fragment length after chain-end clipping (0 = slot unused), bit 31 = SE reverse strand
   uint32_t k;       // ordinal of the fragment inside its window
   uint64_t foff;    // offset of the fragment's first base in the chains buffer
+  uint64_t pad;
+};
+
+// What fragment_kernel needs of a fragment's window, 48 bytes side by side: made once when the batch is planned
+// (batch_map_kernel), so that a lane gathers one row where it would follow the window to its chain and its segment.
+struct WinRow {
+  uint64_t hap_off;   // chain_off + hap_base: where the window's position 0 lies in the chains buffer
+  uint64_t room;      // chain_len - hap_base: bases from position 0 to the chain's end
+  uint32_t spos, len; // of the sg_window
+  uint32_t slot_base, seg_size;
+  uint32_t name0;     // slot_base - the first slot of the window's segment: its name base while the segment is not flagged
+  uint32_t flags;     // bit 0: edge window, bit 1: its segment is flagged
   uint64_t pad;
 };
 
@@ -52,7 +65,7 @@ struct DevProfile {
   const uint32_t* isz_row; uint32_t isz_lg;  // isz_row == nullptr -> fixed insert size
   int32_t isz_min, fixed_isz;
   int32_t isz_lo, isz_hi;      // smallest / largest insert size that can be drawn
-  // sequencing indels by skipping ahead (indel_kernel): evA / 2^64 = P(insertion at a position), evB / 2^64 = P(insertion or
+  // sequencing indels by skipping ahead (fragment_kernel): evA / 2^64 = P(insertion at a position), evB / 2^64 = P(insertion or
   // deletion); gap_row[k] = P(no candidate in the next k positions) * 2^64, k = 1 .. L ([0] unused)
   uint64_t evA, evB;
   const uint64_t* gap_row;
@@ -88,16 +101,22 @@ struct DevBatch {
   uint32_t k0, k1;              // philox key
   uint32_t diag;                // SG_DIAG timing ablations (0 in production; outputs are wrong otherwise)
   uint32_t strict_bases;        // 1: a literal X of the genome is an unknown base (sg_set_strict_bases); 0: the trie's place holder
+  // made when the batch is planned (batch_map_kernel)
+  uint32_t* win_slot;           // [n_windows + 1] the windows' slot_base side by side, [n_windows] = n_slots
+  uint32_t* win_flag;           // [n_windows] bit 0: edge window (an attempt can fail); bits 1..: its segment (by seg_first_window)
+  WinRow* win_rows;             // [n_windows]
+  uint32_t* blk_win;            // [ceil(n_slots / 256)] the window that owns slot 256 b
+  uint32_t* seg_flag;           // [n_segs] the segment holds an edge window
+  uint32_t* seg_lost;           // [n_segs] planned fragments the segment's edge windows gave up (edge_kernel; 0 elsewhere)
   // work buffers
-  PairRec* pairs;               // [n_slots]
-  uint32_t* win_actual;         // [n_windows] fragments actually produced per window
-  uint32_t* win_namebase;       // [n_windows] fragments produced by earlier windows of the same segment
+  PairRec* pairs;               // [n_slots] the fragments of edge windows (edge_kernel); other slots are not written
+  uint32_t* win_namebase;       // [n_windows] fragments produced by earlier windows of the same segment: segments with seg_flag only
   uint32_t* events;             // [2][n_slots][SG_MAX_EVENTS]
-  uint32_t* recloc;             // [2][n_slots] exclusive prefix of reclen inside the read's block of 256 (indel_kernel)
+  uint32_t* recloc;             // [2][n_slots] exclusive prefix of reclen inside the read's block of 256 (fragment_kernel)
   uint64_t* blkbase;            // [2][ceil(n_slots / 256)] offset of a block's first record inside its segment of 2^seg_shift blocks
-                                // (sums by indel_kernel, scanned in place by block_base_kernel; the segments' own bases: totals + kTotalsSegBase)
+                                // (sums by fragment_kernel, scanned in place by block_base_kernel; the segments' own bases: totals + kTotalsSegBase)
   uint32_t seg_shift;
-  uint4* meta;                  // [2][n_slots][3] per-read 48-byte rows for the emit kernels: m0, m1, name text (indel_kernel)
+  uint4* meta;                  // [2][n_slots][3] per-read 48-byte rows for the emit kernels: m0, m1, name text (fragment_kernel)
   // (from byte 128 on: the emit kernels' read-group counters, one 128-byte line each, see GroupRuns in sg_emit.h)
   uint64_t* totals;             // [0],[1] bytes per mate; [2] fragments produced; [3] flags (1 events, 2 slow queue full); [4] slow-queue counts;
   uint2* slowq;                 // [2][slowq_cap] (slot, item) left to emit_slow_kernel by the fast emit kernel
@@ -108,9 +127,9 @@ struct DevBatch {
 };
 
 // ---- launchers of the sampling pass (sg_kernels.hip; the straight-line kernel's own, launch_emit_fast, in sg_emit.h); the window planner's are in sg_windows.h, the scan's in sg_scan.h ----
-void launch_plan(const DevProfile& P, const DevBatch& B, hipStream_t s);
-void launch_namebase(const DevBatch& B, hipStream_t s);
-void launch_indel(const DevProfile& P, const DevBatch& B, hipStream_t s);
+void launch_batch_map(const DevProfile& P, const DevBatch& B, hipStream_t s);   // at plan time; seg_flag, seg_lost cleared before
+void launch_edge(const DevProfile& P, const DevBatch& B, hipStream_t s);
+void launch_fragment(const DevProfile& P, const DevBatch& B, hipStream_t s);
 void launch_scan(const DevBatch& B, hipStream_t s);
 void launch_mail(const uint64_t* totals, uint64_t* mail, hipStream_t s);   // totals[0..4] -> pinned host words
 void launch_header(const DevProfile& P, const DevBatch& B, hipStream_t s);

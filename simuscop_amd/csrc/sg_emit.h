@@ -1,4 +1,4 @@
-// sg_emit.h -- what the emit kernels of sg_kernels.hip (generic, slow, header, and indel_kernel as the rows' writer) and
+// sg_emit.h -- what the emit kernels of sg_kernels.hip (generic, slow, header, and fragment_kernel as the rows' writer) and
 // the straight-line kernel of sg_emit_fast.hip share: the workgroup shape, the read row, the straight-line kernel's LDS
 // layout, the read-group runs and the few device helpers both files call.  Device code (.hip files only).
 #pragma once
@@ -12,7 +12,7 @@ namespace sg {
 #define META_ROW 32  // bytes of LDS metadata per read
 
 // ------------------------------------------------------------------------------------------------
-// The read row: DevBatch::meta holds 48 bytes per read, written by indel_kernel (m0 and m1 through ReadRow::make_m0 and
+// The read row: DevBatch::meta holds 48 bytes per read, written by fragment_kernel (m0 and m1 through ReadRow::make_m0 and
 // ReadRow::make_m1, then the name's text), read by every emit kernel and by header_kernel.
 //   m0 (bytes 0..15)   x, y  offset of the fragment's first base in the chains buffer (low, high word)
 //                      z     namepos   } the two numbers of the read's name "@popu#chr#pos%segsize#fragCount[/m]"
@@ -80,7 +80,7 @@ struct ReadRow {
   uint4 m0, m1;
   __device__ __forceinline__ static ReadRow load(const uint4* meta, size_t idx) { return ReadRow{meta[idx * 3], meta[idx * 3 + 1]}; }
   __device__ __forceinline__ static ReadRow none() { return ReadRow{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)}; }
-  // the writer's side (indel_kernel): the two words of a live read; an unused slot's are all zero
+  // the writer's side (fragment_kernel): the two words of a live read; an unused slot's are all zero
   __device__ __forceinline__ static uint4 make_m0(uint64_t foff, uint32_t namepos, uint32_t fragcount) {
     return make_uint4((uint32_t)foff, (uint32_t)(foff >> 32), namepos, fragcount);
   }
@@ -207,13 +207,32 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// A workgroup barrier for what its waves hand each other through LDS only: their LDS operations are ordered, their
+// global loads and stores stay in flight across it (__syncthreads() waits for those too: s_waitcnt vmcnt(0)).
+__device__ __forceinline__ void block_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // Byte offset of read t's record in its mate's text: base of its segment of 2^seg_shift blocks + base of its block of
-// 256 reads inside the segment + prefix inside the block (indel_kernel, block_base_kernel)
+// 256 reads inside the segment + prefix inside the block (fragment_kernel, block_base_kernel)
 __device__ __forceinline__ uint64_t rec_offset(const DevBatch& B, uint32_t m, uint32_t t) {
   const uint32_t blk = t >> 8;
   const uint64_t* segbase = (const uint64_t*)((const uint8_t*)B.totals + kTotalsSegBase);
   return segbase[m * 16u + (blk >> B.seg_shift)] + B.blkbase[(size_t)m * ((B.n_slots + 255u) >> 8) + blk] +
          B.recloc[(size_t)m * B.n_slots + t];
+}
+
+// The window that owns slot t: the last one that starts at or before it (empty windows share their slot_base with the
+// next window that owns slots).  fragment_kernel finds its 256 windows block-wise; this is for single look-ups.
+__device__ __forceinline__ uint32_t slot_window(const DevBatch& B, uint32_t t) {
+  uint64_t lo = 0, hi = B.n_windows;  // win_slot[lo] <= t < win_slot[hi]
+  while (lo + 1u < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (B.win_slot[mid] <= t) lo = mid; else hi = mid;
+  }
+  return (uint32_t)lo;
 }
 
 __device__ __forceinline__ uint32_t aux_draw(const DevBatch& B, uint32_t slot, uint32_t j, uint32_t f, uint32_t mate) {

@@ -155,7 +155,7 @@ __host__ __device__ inline uint32_t truth_reg2bin(int64_t beg, int64_t end) {
   return 0;
 }
 
-// What the pass left of read (t, m): the meta row of indel_kernel and the fragment's window
+// What the pass left of read (t, m): the meta row of fragment_kernel and the fragment's window
 struct ReadGeom {
   bool live, inside;      // inside: the template lies in its chain
   uint32_t chain, reverse, np, nev, hdr;
@@ -175,9 +175,9 @@ __device__ __forceinline__ ReadGeom read_geom(const DevProfile& P, const DevBatc
   const uint32_t L = (uint32_t)P.L;
   g.reverse = rd.rev() ? 1u : 0u;
   g.np = rd.np();
-  g.nev = rd.nev();   // the row's count: indel_kernel drops the events of a read that would get shorter than 50
+  g.nev = rd.nev();   // the row's count: fragment_kernel drops the events of a read that would get shorter than 50
   g.hdr = rd.hdr_len();
-  g.chain = B.windows[B.pairs[t].win].chain;
+  g.chain = B.windows[slot_window(B, t)].chain;
   const uint64_t c0 = B.chain_off[g.chain], tmpl = g.reverse ? foff + flen - L : foff;
   g.inside = flen >= L && tmpl >= c0 && tmpl - c0 + L <= B.chain_len[g.chain];
   g.tmpl_off = tmpl - c0;

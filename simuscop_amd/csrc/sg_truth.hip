@@ -12,7 +12,7 @@
 //                       comes in as 16-byte pieces, its image is put together byte by byte in LDS (name, operations,
 //                       4-bit bases, qualities; turned round for a reverse read), and leaves as 16-byte pieces --
 //                       records are ~300 unaligned bytes, stored by their own lanes every store instruction would
-//                       touch 64 cache lines (the reason indel_kernel's rows leave through LDS); only the bytes an
+//                       touch 64 cache lines (the reason fragment_kernel's rows leave through LDS); only the bytes an
 //                       image shares a 16-byte piece with its neighbours' go out singly.  truth_pack_kernel<true>
 //                       (simuReads --truth-tags) appends the NM, XE and MD tags that truth_tag_size_kernel
 //                       (sg_truth_tags.hip) has sized; truth_pack_kernel<false> is the kernel without them.
