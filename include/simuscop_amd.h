@@ -101,7 +101,8 @@ void sg_profile_tables_free(sg_profile_tables* tables);
  * (lib/segment/Segment.cpp:448-458; NULL entries contribute nothing).  A fragment that runs past
  * its segment continues into the following segments' same-index haplotype
  * (Segment::getFragSequence :1085-1101 -> Genome::produceFragment, Genome.cpp:599-632): on a chain
- * that is a plain substring, clipped at the chain end.  Bytes are upper-case ASCII.             */
+ * that is a plain substring, clipped at the chain end.  Bytes are ASCII; letters of either case
+ * get the codes sg_build_haplotypes gives them (the driver uploads upper case).                 */
 int sg_upload_haplotypes(sg_ctx* ctx, int32_t n_chains, const char* const* chains, const uint64_t* lens);
 
 /* ---- reference ingest and haplotype assembly on the device ------------------ */
@@ -144,11 +145,18 @@ typedef struct sg_hap_patch {
   uint32_t chain;
   uint32_t base;    /* ASCII, any case         */
 } sg_hap_patch;
-/* Pieces must tile every chain exactly (no byte of [0, lens[c]) left out); patches apply afterwards. */
+/* Pieces must tile every chain exactly: ordered by dst, the pieces of chain c follow one another from 0 to lens[c]
+ * without a gap and without an overlap.  They may come in any order, chains interleaved (a list already in dst order
+ * chain by chain is checked in one pass, any other is sorted first); pieces of length 0 are allowed anywhere inside
+ * their chain and source.  A piece outside its chain or its source, a gap and an overlap -- also an overlap that a gap
+ * of the same size makes up for in the sum -- are SG_ERR_INVALID naming the piece or the chain, before anything is
+ * launched; no range is too large to be told (offsets near 2^64 are refused like any other).  Patches apply afterwards;
+ * two patches on one base leave either.                                                              */
 int sg_build_haplotypes(sg_ctx* ctx, int32_t n_chains, const uint64_t* lens, const sg_hap_piece* pieces, uint64_t n_pieces,
                         const char* literals, uint64_t n_literal_bytes, const sg_hap_patch* patches, uint64_t n_patches);
 /* Diagnostic read-back of the resident chains (either upload route): base codes A0 C1 T2 G3, 'N' = 4,
- * any other character = 5.                                                                        */
+ * 'X' = 6 (letters in either case), any other character = 5.  A range that does not lie inside the
+ * chain is SG_ERR_INVALID.                                                                         */
 int sg_haplotype_codes(sg_ctx* ctx, uint32_t chain, uint64_t offset, uint64_t n, uint8_t* codes_out);
 
 /* ---- sampling plan ------------------------------------------------------------------------ */

@@ -4,6 +4,9 @@
 #include <algorithm>
 
 #include "sg_api.h"
+#include "sg_hap_check.h"
+
+namespace chk = sg::hapcheck;
 
 // 2-bit copies of the chains buffer (`total` bytes, a multiple of 1024) for the straight-line emit kernel
 static int pack_chains(sg_ctx* ctx, size_t total) {
@@ -68,7 +71,7 @@ int sg_reference_begin(sg_ctx* ctx, uint64_t raw_bytes) {
 
 int sg_reference_chunk(sg_ctx* ctx, uint64_t offset, const void* host, uint64_t bytes) {
   if (!ctx || (!host && bytes)) return SG_ERR_INVALID;
-  if (!ctx->ref_raw.p || offset + bytes > ctx->ref_raw_bytes) return ctx->fail(SG_ERR_INVALID, "sg_reference_chunk: range outside sg_reference_begin's size");
+  if (auto v = chk::chunk(ctx->ref_raw.p != nullptr, ctx->ref_raw_bytes, offset, bytes)) return ctx->fail(v.code, v.msg);
   SG_HIP(hipSetDevice(ctx->device));
   if (bytes) SG_HIP(hipMemcpyAsync((uint8_t*)ctx->ref_raw.p + offset, host, bytes, hipMemcpyHostToDevice, ctx->stream));
   return SG_OK;
@@ -76,7 +79,7 @@ int sg_reference_chunk(sg_ctx* ctx, uint64_t offset, const void* host, uint64_t 
 
 int sg_reference_scan(sg_ctx* ctx, uint64_t* header_offsets, uint32_t cap, uint32_t* n_found, uint32_t* flags) {
   if (!ctx || !n_found || (cap && !header_offsets)) return SG_ERR_INVALID;
-  if (!ctx->ref_raw.p) return ctx->fail(SG_ERR_INVALID, "sg_reference_scan: call sg_reference_begin first");
+  if (auto v = chk::need_image(ctx->ref_raw.p != nullptr, "sg_reference_scan")) return ctx->fail(v.code, v.msg);
   SG_HIP(hipSetDevice(ctx->device));
   SG_ENSURE(ctx->hap_work, (size_t)cap * 8 + 64);
   uint32_t* counters = (uint32_t*)((uint8_t*)ctx->hap_work.p + (size_t)cap * 8);
@@ -93,19 +96,13 @@ int sg_reference_scan(sg_ctx* ctx, uint64_t* header_offsets, uint32_t cap, uint3
 
 int sg_reference_commit(sg_ctx* ctx, const sg_contig* contigs, uint32_t n_contigs) {
   if (!ctx || (n_contigs && !contigs)) return SG_ERR_INVALID;
-  if (!ctx->ref_raw.p) return ctx->fail(SG_ERR_INVALID, "sg_reference_commit: call sg_reference_begin first");
+  if (auto v = chk::need_image(ctx->ref_raw.p != nullptr, "sg_reference_commit")) return ctx->fail(v.code, v.msg);
   SG_HIP(hipSetDevice(ctx->device));
   std::vector<sg::DevContig> tab(n_contigs);
   uint64_t code_off = 0, blocks = 0;
   for (uint32_t c = 0; c < n_contigs; c++) {
     const sg_contig& k = contigs[c];
-    if (k.length && (k.line_bases == 0 || k.line_width < k.line_bases))
-      return ctx->fail(SG_ERR_INVALID, "sg_reference_commit: contig " + std::to_string(c) + " has an impossible line shape");
-    if (k.length > 0xFFFFFFF0ull)   // (the ingest kernel's line / column arithmetic is 32-bit; the host says the same, fasta.cpp)
-      return ctx->fail(SG_ERR_UNSUPPORTED, "sg_reference_commit: contig " + std::to_string(c) + " is longer than 4 Gbp");
-    const uint64_t lines = k.length ? (k.length - 1) / k.line_bases : 0;  // line breaks inside the contig
-    if (k.raw_offset + k.length + lines * (k.line_width - k.line_bases) > ctx->ref_raw_bytes)
-      return ctx->fail(SG_ERR_INVALID, "sg_reference_commit: contig " + std::to_string(c) + " runs past the end of the file");
+    if (auto v = chk::contig(k, c, ctx->ref_raw_bytes)) return ctx->fail(v.code, v.msg);   // line shape, 32-bit length, extent
     tab[c] = sg::DevContig{k.raw_offset, code_off, k.length, k.line_bases, k.line_width, blocks};
     blocks += (k.length + 15) / 16;
     code_off += ((k.length + 15) / 16) * 16 + 64;
@@ -130,40 +127,27 @@ int sg_build_haplotypes(sg_ctx* ctx, int32_t n_chains, const uint64_t* lens, con
   if (!ctx || n_chains < 0 || (n_chains && !lens) || (n_pieces && !pieces) || (n_patches && !patches) ||
       (n_literal_bytes && !literals))
     return SG_ERR_INVALID;
-  if (ctx->ref_contigs.empty() && n_pieces) return ctx->fail(SG_ERR_INVALID, "sg_build_haplotypes: call sg_reference_commit first");
+  if (auto v = chk::need_contigs(!ctx->ref_contigs.empty(), n_pieces)) return ctx->fail(v.code, v.msg);
   SG_HIP(hipSetDevice(ctx->device));
   sg_ctx::ChainLayout L = chain_layout(n_chains, lens);
-  // absolute offsets, long pieces split so that every workgroup moves <= 64 KB; coverage is checked
-  // by summing the piece lengths per chain after a bounds check of each piece
+  // absolute offsets, long pieces split so that every workgroup moves <= 64 KB; each piece is checked against its chain
+  // and its source, then the list as a tiling of every chain (sg_hap_check.h)
   const uint32_t kSplit = 1u << 16;
   std::vector<sg::DevPiece> dp;
   dp.reserve((size_t)n_pieces + L.total / kSplit + 16);
-  std::vector<uint64_t> covered((size_t)n_chains, 0);
+  auto contig_length = [&](uint32_t k) { return ctx->ref_contigs[k].length; };
   for (uint64_t i = 0; i < n_pieces; i++) {
     const sg_hap_piece& p = pieces[i];
-    if ((int64_t)p.chain >= n_chains || p.dst + p.len > lens[p.chain])
-      return ctx->fail(SG_ERR_INVALID, "sg_build_haplotypes: piece " + std::to_string(i) + " falls outside its chain");
-    uint64_t src;
-    if (p.kind == 0) {
-      if (p.contig >= ctx->ref_contigs.size() || p.src + p.len > ctx->ref_contigs[p.contig].length)
-        return ctx->fail(SG_ERR_INVALID, "sg_build_haplotypes: piece " + std::to_string(i) + " falls outside its contig");
-      src = ctx->ref_contigs[p.contig].code_off + p.src;
-    } else {
-      if (p.src + p.len > n_literal_bytes)
-        return ctx->fail(SG_ERR_INVALID, "sg_build_haplotypes: piece " + std::to_string(i) + " falls outside the literal bytes");
-      src = p.src;
-    }
-    covered[p.chain] += p.len;
+    if (auto v = chk::piece(p, i, n_chains, lens, contig_length, ctx->ref_contigs.size(), n_literal_bytes)) return ctx->fail(v.code, v.msg);
+    const uint64_t src = p.kind == 0 ? ctx->ref_contigs[p.contig].code_off + p.src : p.src;
     for (uint32_t o = 0; o < p.len; o += kSplit)
       dp.push_back(sg::DevPiece{L.off[p.chain] + p.dst + o, src + o, std::min<uint32_t>(kSplit, p.len - o), p.kind ? 1u : 0u});
   }
-  for (int c = 0; c < n_chains; c++)
-    if (covered[c] != lens[c]) return ctx->fail(SG_ERR_INVALID, "sg_build_haplotypes: the pieces of chain " + std::to_string(c) + " do not add up to its length");
+  if (auto v = chk::tiling(n_chains, lens, pieces, n_pieces)) return ctx->fail(v.code, v.msg);
   std::vector<sg::DevPatch> pt((size_t)n_patches);
   for (uint64_t i = 0; i < n_patches; i++) {
     const sg_hap_patch& q = patches[i];
-    if ((int64_t)q.chain >= n_chains || q.dst >= lens[q.chain])
-      return ctx->fail(SG_ERR_INVALID, "sg_build_haplotypes: patch " + std::to_string(i) + " falls outside its chain");
+    if (auto v = chk::patch(q, i, n_chains, lens)) return ctx->fail(v.code, v.msg);
     pt[i] = sg::DevPatch{L.off[q.chain] + q.dst, q.base, 0};
   }
   SG_ENSURE(ctx->chains, L.total);
@@ -190,10 +174,8 @@ int sg_build_haplotypes(sg_ctx* ctx, int32_t n_chains, const uint64_t* lens, con
 
 int sg_haplotype_codes(sg_ctx* ctx, uint32_t chain, uint64_t offset, uint64_t n, uint8_t* codes_out) {
   if (!ctx || (n && !codes_out)) return SG_ERR_INVALID;
-  if (!ctx->have_haps) return ctx->fail(SG_ERR_INVALID, "sg_haplotype_codes: no haplotypes on the device");
+  if (auto v = chk::codes(ctx->have_haps, ctx->hap.len.data(), ctx->hap.len.size(), chain, offset, n)) return ctx->fail(v.code, v.msg);
   SG_HIP(hipSetDevice(ctx->device));
-  if (chain >= ctx->hap.len.size()) return ctx->fail(SG_ERR_INVALID, "sg_haplotype_codes: chain index out of range");
-  if (offset + n > ctx->hap.len[chain]) return ctx->fail(SG_ERR_INVALID, "sg_haplotype_codes: range past the end of the chain");
   if (n) SG_HIP(hipMemcpy(codes_out, ctx->B.chains + ctx->hap.off[chain] + offset, n, hipMemcpyDeviceToHost));
   return SG_OK;
 }

@@ -959,7 +959,7 @@ __device__ __forceinline__ uint32_t encode4(uint32_t w) {
   uint32_t o = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    const uint32_t b = (w >> (8 * i)) & 0xFFu;
+    const uint32_t b = (w >> (8 * i)) & 0xDFu;   // letters in either case, as encode_base of sg_haplotypes.hip has them
     const bool acgt = (b == 'A') | (b == 'C') | (b == 'G') | (b == 'T');
     const uint32_t v = acgt ? ((b >> 1) & 3u) : (b == 'N' ? 4u : (b == 'X' ? 6u : 5u));
     o |= v << (8 * i);
