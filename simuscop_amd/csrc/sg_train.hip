@@ -500,7 +500,9 @@ __device__ __forceinline__ void count_base(const TrainJob& J, const TrainRead& R
   const uint8_t* ref = J.ref_codes + R.ref_off;
   const uint8_t* alt = J.alt_codes + R.ref_off;
   // index in `bases` of the base the k-mer context holds at read position q (:404-415: the alternative allele where the
-  // read shows it, else the reference base), and whether the read shows the alternative allele there
+  // read shows it, else the reference base), and whether the read shows the alternative allele there.  -2: a literal 'X'
+  // (in the genome, code 6, or a known allele the read shows, its character), which the reference's trie takes for the
+  // place holder in front of a read's first bases (:94-101, :220-226); on the reverse strand it complements to 'N'
   auto context_idx = [&](uint32_t q, bool* is_alt) -> int {
     const uint32_t w = rev ? n - 1u - q : q;
     uint32_t code = ref[w];
@@ -516,7 +518,7 @@ __device__ __forceinline__ void count_base(const TrainJob& J, const TrainRead& R
         if (eq) { code = ac; *is_alt = true; }
       }
     }
-    if (code > 3u) return -1;
+    if (code > 3u) return (!rev && (code == 6u || code == (uint32_t)'X')) ? -2 : -1;
     if (rev) code ^= 2u;
     return (int)((J.remap >> (2u * code)) & 3u);
   };
@@ -530,16 +532,19 @@ __device__ __forceinline__ void count_base(const TrainJob& J, const TrainRead& R
   bool shows_alt;
   const int s0 = context_idx(i, &shows_alt);
   if (b >= 0) {                                      // :416-442
-    const uint32_t m = i + 1u < K ? i + 1u : K;       // real bases of the context, the rest is 'X'
-    int kidx = (int)J.kmer_off[m];
+    const uint32_t m = i + 1u < K ? i + 1u : K;       // read positions of the context, the rest is 'X'
+    uint32_t real = 0;                                // bases behind the place holders: the trie holds X..Xb..b only
+    bool in_trie = true;
     int v = 0;
     for (uint32_t t = 0; t < m; t++) {                // oldest base in the highest digit
       bool dummy;
       const int x = t + 1u == m ? s0 : context_idx(i + 1u - m + t, &dummy);
-      if (x < 0) { kidx = -1; break; }
+      if (x == -2 && real == 0u) continue;            // a literal X in front of every base: one more place holder
+      if (x < 0) { in_trie = false; break; }
       v = v * 4 + x;
+      real++;
     }
-    if (kidx >= 0) sink.sub(rev, (uint32_t)(kidx + v), bin, (uint32_t)b);
+    if (in_trie && real) sink.sub(rev, J.kmer_off[real] + (uint32_t)v, bin, (uint32_t)b);
   }
   if ((R.flags & 4u) && b >= 0) {                    // :457-480
     uint32_t rc = ref[j];                            // refSeq[i] itself must be a base (:460,463) ...

@@ -18,34 +18,12 @@ import cases
 import histo_util as H
 import simuscop_amd
 import train_util as TU
-from simuscop_amd import SgContig
+from train_lines import reference_on_device as _reference_on_device, setup_from_files as _setup_from_files
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIMU = os.path.join(ROOT, "simuscop_amd", "lib", "simuReads")
-
-
-def _reference_on_device(eng, ctx, fasta_path, line_len=60):
-    image = open(fasta_path, "rb").read()
-    assert eng.sg_reference_begin(ctx, len(image)) == 0
-    assert eng.sg_reference_chunk(ctx, 0, image, len(image)) == 0
-    assert eng.sg_sync(ctx) == 0
-    rows, keys, off = [], [], 0
-    while off < len(image):                      # headers and bodies of a write_fasta file
-        assert image[off:off + 1] == b">"
-        e = image.index(b"\n", off)
-        name = image[off + 1:e].split()[0]
-        nxt = image.find(b">", e)
-        body_end = len(image) if nxt < 0 else nxt
-        body = image[e + 1:body_end]
-        length = len(body) - body.count(b"\n")
-        rows.append(SgContig(e + 1, length, line_len, line_len + 1))
-        keys.append(name[3:] if name.startswith(b"chr") else name)
-        off = body_end
-    tab = (SgContig * len(rows))(*rows)
-    assert eng.sg_reference_commit(ctx, tab, len(rows)) == 0, eng.sg_last_error(ctx)
-    return keys
 
 
 ARRAYS = ("subs1", "subs2", "kmers", "quality", "isize", "ins_len", "del_len")
@@ -122,74 +100,7 @@ def _sampled_lines(oracle_lib, wd, profile="xten", insert=350, coverage=10):
     return lines, fa, T
 
 
-def _setup_from_files(keys, lens, vcf, bed, T, keep):
-    """sg_train_setup from the VCF / BED files, parsed here the way vcfparser.cpp:26-106 and Genome.cpp:238-299, 684-739 do (the
-    product's own parsers are exercised through `seqToProfile` below)."""
-    row = {k: i for i, k in enumerate(keys)}
-    abbr = lambda n: n.split(b"chrom", 1)[1] if b"chrom" in n else (n.split(b"chr", 1)[1] if b"chr" in n else n)   # noqa: E731
-    snv, ins, dele = [], [], []
-    for line in open(vcf, "rb"):
-        if line.startswith(b"#"):
-            continue
-        f = line.split(b"\t")   # (the line break stays with the last field, as after fgets: "1/1\n" is not "1/1")
-        if len(f) < 10:
-            continue
-        info = f[7]
-        if b"DP=" in info and int(info.split(b"DP=", 1)[1].split(b";", 1)[0]) < 10:
-            continue
-        if float(f[5]) < 20:
-            continue
-        c = row.get(abbr(f[0]))
-        if c is None:
-            continue
-        pos, homo = int(f[1]), f[9].split(b":")[0] != b"1/1"
-        if len(f[3]) > 1:
-            dele.append((c, pos + 1, len(f[3]) - 1))
-        elif len(f[4]) > 1:
-            ins.append((c, pos, len(f[4]) - 1))
-        else:
-            snv.append((c, pos, f[4][:1], 1 if homo else 0))
-    st = simuscop_amd.SgTrainSetup()
-    karr = (C.c_char_p * len(keys))(*keys)
-    keep += [karr]
-    st.contig_keys, st.n_contigs, st.bases, st.kmer, st.bins = karr, len(keys), T.bases.encode(), 3, T.bins
-    st.n_isize, st.n_indel_len, st.count_gc, st.window = 2048, 256, 1, 1000
-
-    def arr(ctype, vals):
-        a = (ctype * max(1, len(vals)))(*vals)
-        keep.append(a)
-        return a
-    st.n_snv = len(snv)
-    st.snv_contig, st.snv_pos = arr(C.c_uint32, [x[0] for x in snv]), arr(C.c_int64, [x[1] for x in snv])
-    alt = b"".join(x[2] for x in snv)
-    keep.append(alt)
-    st.snv_alt, st.snv_homo = alt, arr(C.c_uint8, [x[3] for x in snv])
-    st.n_ins, st.ins_contig, st.ins_pos, st.ins_len = len(ins), arr(C.c_uint32, [x[0] for x in ins]), arr(C.c_int64, [x[1] for x in ins]), arr(C.c_int32, [x[2] for x in ins])
-    st.n_del, st.del_contig, st.del_pos, st.del_len = len(dele), arr(C.c_uint32, [x[0] for x in dele]), arr(C.c_int64, [x[1] for x in dele]), arr(C.c_int32, [x[2] for x in dele])
-    if bed:
-        per = {}
-        for line in open(bed, "rb"):
-            f = line.rstrip(b"\n").split(b"\t")
-            c = row.get(abbr(f[0]))
-            if c is None or lens[c] <= 0:
-                continue
-            e = int(f[2])
-            sp, ep = max(1, int(f[1]) - 50 + 1), min(lens[c], (lens[c] - (-e) % lens[c] if e <= 0 else e) + 50)
-            k, s0 = (ep - sp + 1) // 1000, sp
-            for i in range(max(k, 0)):
-                e0 = ep if i == k - 1 else s0 + 999
-                per.setdefault(c, []).append((s0, e0))
-                s0 = e0 + 1
-            if s0 <= ep:
-                per.setdefault(c, []).append((s0, ep))
-        first, sp, ep = [0], [], []
-        for c in range(len(keys)):
-            for a, b in per.get(c, []):
-                sp.append(a)
-                ep.append(b)
-            first.append(len(sp))
-        st.target_first, st.target_spos, st.target_epos = arr(C.c_uint64, first), arr(C.c_int64, sp), arr(C.c_int64, ep)
-    return st
+# (sg_train_setup from the VCF / BED files: tests/train_lines.py holds the parsing)
 
 
 @pytest.mark.parametrize("exome", [False, True])
