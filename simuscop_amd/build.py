@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 INCLUDE = os.path.join(ROOT, "include")
 
-ENGINE_SRCS = ["sg_kernels.hip", "sg_emit_fast.hip", "sg_scan.hip", "sg_windows.hip", "sg_haplotypes.hip", "sg_deflate.hip", "sg_train.hip", "sg_inflate.hip", "sg_bam.hip", "sg_truth.hip", "sg_truth_tags.hip", "sg_bamsort.hip", "sg_bamindex.hip", "sg_depth.hip", "sg_variants.hip", "sg_errors.hip", "sg_vcf.hip", "sg_eval.hip", "sg_memory.cpp", "sg_api.cpp", "sg_profile_tables.cpp", "sg_api_deflate.cpp", "sg_api_truth.cpp", "sg_api_haplotypes.cpp", "sg_api_windows.cpp", "sg_api_train.cpp", "sg_api_bgzf.cpp", "sg_api_depth.cpp", "sg_api_variants.cpp", "sg_api_errors.cpp", "sg_api_truth_tags.cpp", "sg_api_bamsort.cpp", "sg_api_bamindex.cpp", "sg_api_vcf.cpp", "sg_api_eval.cpp", "sg_tables.cpp", "sg_deflate.cpp"]
+ENGINE_SRCS = ["sg_pass_front.hip", "sg_kernels.hip", "sg_emit_fast.hip", "sg_scan.hip", "sg_windows.hip", "sg_haplotypes.hip", "sg_deflate.hip", "sg_train.hip", "sg_inflate.hip", "sg_bam.hip", "sg_truth.hip", "sg_truth_tags.hip", "sg_bamsort.hip", "sg_bamindex.hip", "sg_depth.hip", "sg_variants.hip", "sg_errors.hip", "sg_vcf.hip", "sg_eval.hip", "sg_memory.cpp", "sg_api.cpp", "sg_profile_tables.cpp", "sg_api_deflate.cpp", "sg_api_truth.cpp", "sg_api_haplotypes.cpp", "sg_api_windows.cpp", "sg_api_train.cpp", "sg_api_bgzf.cpp", "sg_api_depth.cpp", "sg_api_variants.cpp", "sg_api_errors.cpp", "sg_api_truth_tags.cpp", "sg_api_bamsort.cpp", "sg_api_bamindex.cpp", "sg_api_vcf.cpp", "sg_api_eval.cpp", "sg_tables.cpp", "sg_deflate.cpp"]
 HOST_SRCS = ["host/config.cpp", "host/profile.cpp", "host/fasta.cpp", "host/variants.cpp", "host/genome.cpp",
              "host/simulate.cpp", "host/read_plan.cpp", "host/fastq_sink.cpp", "host/truth_bam.cpp", "host/truth_outputs.cpp", "host/truth_variants.cpp", "host/truth_errors.cpp", "host/truth_sort.cpp", "host/truth_sort_tiles.cpp", "host/truth_index.cpp",
              "host/train.cpp", "host/eval.cpp"]

@@ -126,11 +126,11 @@ static int launch_text(sg_ctx* ctx, bool prof) {
     B.slowq = ctx->slowq.as<uint2>();
     B.slowq_cap = (uint32_t)cap;
   }
-  if (prof) SG_HIP(hipEventRecord(ctx->evs[5], s));  // after the (first-pass) output allocation
+  if (prof) SG_HIP(hipEventRecord(ctx->evs[sg_ctx::EV_TEXT_BEGIN], s));  // after the (first-pass) output allocation
   sg::launch_header(ctx->P, B, s);
   ctx->pass.emit_path = sg::emit_path(ctx->P, B, false);
-  sg::launch_emit(ctx->P, B, s, false, prof ? ctx->evs[7] : nullptr);
-  if (prof) SG_HIP(hipEventRecord(ctx->evs[6], s));
+  sg::launch_emit(ctx->P, B, s, false, prof ? ctx->evs[sg_ctx::EV_MAIN_EMIT_END] : nullptr);
+  if (prof) SG_HIP(hipEventRecord(ctx->evs[sg_ctx::EV_TEXT_END], s));
   return SG_OK;
 }
 
@@ -157,16 +157,15 @@ static int run_pass(sg_ctx* ctx) {
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
   if (!B.n_windows) SG_HIP(hipMemsetAsync(B.totals, 0, sg::kTotalsBytes, s));  // (otherwise edge_kernel clears them)
-  // the six intervals of SG_K_NAMES: "plan" is edge_kernel, "namebase" is empty (the numbers are made in the other two),
-  // "indel" is fragment_kernel
-  if (prof) SG_HIP(hipEventRecord(ctx->evs[0], s));
+  // (what the intervals between these events are called: settle_pass)
+  if (prof) SG_HIP(hipEventRecord(ctx->evs[sg_ctx::EV_EDGE_BEGIN], s));
   sg::launch_edge(ctx->P, B, s);
-  if (prof) SG_HIP(hipEventRecord(ctx->evs[1], s));
-  if (prof) SG_HIP(hipEventRecord(ctx->evs[2], s));
+  if (prof) SG_HIP(hipEventRecord(ctx->evs[sg_ctx::EV_EDGE_END], s));
+  if (prof) SG_HIP(hipEventRecord(ctx->evs[sg_ctx::EV_FRAGMENT_BEGIN], s));
   sg::launch_fragment(ctx->P, B, s);
-  if (prof) SG_HIP(hipEventRecord(ctx->evs[3], s));
+  if (prof) SG_HIP(hipEventRecord(ctx->evs[sg_ctx::EV_FRAGMENT_END], s));
   sg::launch_scan(B, s);
-  if (prof) SG_HIP(hipEventRecord(ctx->evs[4], s));
+  if (prof) SG_HIP(hipEventRecord(ctx->evs[sg_ctx::EV_SCAN_END], s));
   SG_HIP(hipGetLastError());
   // a released output set (sg_release_outputs): its buffers become this pass's
   if (ctx->out.empty() && !ctx->spare.empty()) std::swap(ctx->out, ctx->spare.back()->bufs);
@@ -221,9 +220,15 @@ static int settle_pass(sg_ctx* ctx) {
     SG_HIP(hipStreamSynchronize(ctx->stream));
   }
   if (ctx->profiling) {
-    for (int i = 0; i < 4; i++) SG_HIP(hipEventElapsedTime(&ctx->last_ms[i], ctx->evs[i], ctx->evs[i + 1]));
-    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT], ctx->evs[5], ctx->evs[7]));
-    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT_SLOW], ctx->evs[7], ctx->evs[6]));
+    // the six intervals of SG_K_NAMES, by the names they got when each was a kernel of its own: "plan" is edge_kernel,
+    // "namebase" is empty (the numbers are made in the other two), "indel" is fragment_kernel, "scan" is block_base_kernel
+    const hipEvent_t* ev = ctx->evs;
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_PLAN], ev[sg_ctx::EV_EDGE_BEGIN], ev[sg_ctx::EV_EDGE_END]));
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_NAMEBASE], ev[sg_ctx::EV_EDGE_END], ev[sg_ctx::EV_FRAGMENT_BEGIN]));
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_INDEL], ev[sg_ctx::EV_FRAGMENT_BEGIN], ev[sg_ctx::EV_FRAGMENT_END]));
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_SCAN], ev[sg_ctx::EV_FRAGMENT_END], ev[sg_ctx::EV_SCAN_END]));
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT], ev[sg_ctx::EV_TEXT_BEGIN], ev[sg_ctx::EV_MAIN_EMIT_END]));
+    SG_HIP(hipEventElapsedTime(&ctx->last_ms[SG_K_EMIT_SLOW], ev[sg_ctx::EV_MAIN_EMIT_END], ev[sg_ctx::EV_TEXT_END]));
   }
   Q.stage = sg_ctx::Pass::Settled;
   return SG_OK;

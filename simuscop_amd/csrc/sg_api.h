@@ -234,7 +234,10 @@ struct sg_ctx {
   } pass;
 
   bool profiling = false;
-  hipEvent_t evs[8] = {};  // 0-3 starts of plan..scan, 4 end of scan, 5 start of emit, 6 end of emit, 7 between the two emit kernels
+  // the timing events of a pass, in stream order but the last: around edge_kernel, around fragment_kernel, behind
+  // block_base_kernel; before header_kernel, behind the last emit kernel, and between the main emit kernel and emit_slow_kernel
+  enum { EV_EDGE_BEGIN, EV_EDGE_END, EV_FRAGMENT_BEGIN, EV_FRAGMENT_END, EV_SCAN_END, EV_TEXT_BEGIN, EV_TEXT_END, EV_MAIN_EMIT_END, EV_COUNT };
+  hipEvent_t evs[EV_COUNT] = {};
   bool evs_created = false;
   float last_ms[SG_K_COUNT] = {0, 0, 0, 0, 0, 0};
 

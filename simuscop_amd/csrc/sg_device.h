@@ -126,7 +126,7 @@ struct DevBatch {
   uint64_t out_cap[2];
 };
 
-// ---- launchers of the sampling pass (sg_kernels.hip; the straight-line kernel's own, launch_emit_fast, in sg_emit.h); the window planner's are in sg_windows.h, the scan's in sg_scan.h ----
+// ---- launchers of the sampling pass (the front's -- batch_map, edge, fragment, scan, record_seg_shift -- in sg_pass_front.hip, the others in sg_kernels.hip; the straight-line kernel's own, launch_emit_fast, in sg_emit.h); the window planner's are in sg_windows.h, the scan's in sg_scan.h ----
 void launch_batch_map(const DevProfile& P, const DevBatch& B, hipStream_t s);   // at plan time; seg_flag, seg_lost cleared before
 void launch_edge(const DevProfile& P, const DevBatch& B, hipStream_t s);
 void launch_fragment(const DevProfile& P, const DevBatch& B, hipStream_t s);

@@ -1,6 +1,7 @@
-// sg_emit.h -- what the emit kernels of sg_kernels.hip (generic, slow, header, and fragment_kernel as the rows' writer) and
-// the straight-line kernel of sg_emit_fast.hip share: the workgroup shape, the read row, the straight-line kernel's LDS
-// layout, the read-group runs and the few device helpers both files call.  Device code (.hip files only).
+// sg_emit.h -- what the emit kernels of sg_kernels.hip (generic, slow, header), the straight-line kernel of
+// sg_emit_fast.hip and fragment_kernel of sg_pass_front.hip as the rows' writer share: the workgroup shape, the read row,
+// the straight-line kernel's LDS layout, the read-group runs and the few device helpers these files call.  Device code
+// (.hip files only).
 #pragma once
 #include "sg_device.h"
 #include "sg_philox.h"
@@ -225,9 +226,10 @@ __device__ __forceinline__ uint64_t rec_offset(const DevBatch& B, uint32_t m, ui
 }
 
 // The window that owns slot t: the last one that starts at or before it (empty windows share their slot_base with the
-// next window that owns slots).  fragment_kernel finds its 256 windows block-wise; this is for single look-ups.
-__device__ __forceinline__ uint32_t slot_window(const DevBatch& B, uint32_t t) {
-  uint64_t lo = 0, hi = B.n_windows;  // win_slot[lo] <= t < win_slot[hi]
+// next window that owns slots), over win_slot[0 .. n_windows].  `from`: a window known to start at or before t --
+// fragment_kernel looks among 257 staged first slots block-wise and comes here from the last of them.
+__device__ __forceinline__ uint32_t slot_window(const DevBatch& B, uint32_t t, uint32_t from = 0u) {
+  uint64_t lo = from, hi = B.n_windows;  // win_slot[lo] <= t < win_slot[hi]
   while (lo + 1u < hi) {
     const uint64_t mid = (lo + hi) >> 1;
     if (B.win_slot[mid] <= t) lo = mid; else hi = mid;

@@ -311,7 +311,7 @@ __device__ __forceinline__ void flush_fix(const FastBlock<PAIRED, DIAG>& k, Fast
     const uint32_t np = rr.np(), hl = rr.hdr_len();
     // stored like a whole item (a last item of seven bases included), or the read's parked last item?
     const bool whole = 8u * c + 8u <= np + (uint32_t)((np & 7u) == 7u);
-    // ceil(2^32 / n') again (indel_kernel's row word): a read's parked last item has overwritten it in the row
+    // ceil(2^32 / n') again (fragment_kernel's row word): a read's parked last item has overwritten it in the row
     const uint32_t inv = row::inv_of(max(np, 1u));
     while (__ballot(todo != 0u) != 0ull) {
       const bool on = todo != 0u;
@@ -410,7 +410,7 @@ __device__ __forceinline__ void stage_tables(const DevProfile& P, uint32_t tm, u
 }
 
 // The read's name, stored in front of where the step loop will put the bases: the batch's prefix, then the
-// read's own part from its row (indel_kernel made the text), two pieces of <= 16 bytes.  (B.prefix_len <= 16)
+// read's own part from its row (fragment_kernel made the text), two pieces of <= 16 bytes.  (B.prefix_len <= 16)
 template <bool PAIRED>
 __device__ __forceinline__ void store_name(const DevBatch& B, uint32_t m, const ReadRow& my, size_t idx, uint8_t* rec) {
   const uint32_t nv = my.hdr_len() - B.prefix_len;
@@ -1260,7 +1260,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_fast_kernel(DevProfile P, D
 // launch: one 1024-thread workgroup per CU, persistent over read groups; item-stream map, 63 reads per group
 // ------------------------------------------------------------------------------------------------
 // The runtime puts a file's device code on the device when one of its kernels is first used.  While this kernel shared
-// a file with plan_kernel that happened at the pass's first launch; in a file of its own it happened inside the first
+// a file with the pass's first kernel that happened at the pass's first launch; in a file of its own it happened inside the first
 // emit launch's event pair (measured: 0.45 ms on `emit` of a one-pass run's --stats line, 0.3 ms off `plan`,
 // profiles/r14_emit_files/times.txt).  The engine asks for it when a profile that takes this kernel is loaded.
 void preload_emit_fast() {

@@ -1,4 +1,4 @@
-// sg_philox.h -- the counter-based generator of every device draw (device code only: sg_kernels.hip, sg_emit_fast.hip, sg_windows.hip).
+// sg_philox.h -- the counter-based generator of every device draw (device code only: sg_pass_front.hip, sg_kernels.hip, sg_emit_fast.hip, sg_windows.hip).
 // The stream kinds and kBaseRounds are in sg_device.h.
 #pragma once
 #include "sg_device.h"

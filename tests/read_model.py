@@ -6,8 +6,8 @@ A batch is a table of sampling windows (sg_window rows).  Attempt `a` of window 
 single-end read's strand; the fragment is min(bases left in the chain, insert size) long and fails when that is less
 than a read.  A window stops after 1,000 failures (the 1,001st ends it) and leaves the slots it did not fill without a
 record.  Fragment `done` of a window owns the slot slot_base + done (+ first_slot: the draws of a read are addressed by
-the slot in the whole batch), and the name counts the fragments of its segment (oracle.cpp segYieldReads; plan_attempt
-and plan_kernel in sg_kernels.hip).  Mate 1 reads the fragment's first L bases, mate 2 (and a single-end read of strand
+the slot in the whole batch), and the name counts the fragments of its segment (oracle.cpp segYieldReads; plan_attempt,
+edge_kernel and fragment_kernel in sg_pass_front.hip).  Mate 1 reads the fragment's first L bases, mate 2 (and a single-end read of strand
 1) the last L, complemented and reversed; bases and qualities are orc_predict_philox on that template.
 
 `ReadModel.events` restates the indel walk of the oracle's predict (indel_candidate, the length draws, the reset of a

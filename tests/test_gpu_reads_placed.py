@@ -1,4 +1,4 @@
-"""The emit side of a sampling pass (plan_kernel, indel_kernel, header_kernel, emit_fast_kernel, emit_kernel /
+"""The emit side of a sampling pass (edge_kernel, fragment_kernel, header_kernel, emit_fast_kernel, emit_kernel /
 emit_slow_kernel) read by read against tests/read_model.py, on templates the test places by hand.
 
 Per case: the engine context of a Session (so that the profile file goes through host/profile.cpp and
